@@ -3,7 +3,10 @@
 (tokens/sec) on MI355X — the BASELINE.json headline metric.
 
 Usage (driver contract):
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+A plain run sets up, warms up, times the K steps, writes its outputs if
+--dump-outputs is given and prints the result line; anything further the
+benchmark measures or checks belongs behind --full.
 For N>1 the driver launches via torch.distributed.run, one rank per GPU
 over RCCL; this script reads RANK/LOCAL_RANK/WORLD_SIZE/MASTER_* from env.
 
@@ -54,6 +57,46 @@ def build_model(name: str, device, lora_dropout: float,
     return model, cfg
 
 
+DUMP_MAX_ELEMS = 5 << 20       # 20 MB of fp32 per array, 3 arrays < 64 MB
+
+
+def dump_outputs(out_dir: str, loss: float, trainer) -> None:
+    """What a caller of the timed path holds after its last step: the
+    step's returned loss and the optimizer state it updated, in optimizer
+    order (under zero1 this rank's shard) -- the fp32 master copy of the
+    trainable parameters and AdamW's first and second moments.
+
+    The benchmark's schedule is still in its first warmup steps (lr around
+    1e-10), so the parameters barely leave their seeded initial values
+    and the loss is that of the frozen base; the moments are what carries
+    the steps' gradients (attention/LoRA/dropout backward, clipping,
+    AdamW) at full scale.
+
+    Arrays above DUMP_MAX_ELEMS are reduced to a fixed seeded sample:
+    one element from each of DUMP_MAX_ELEMS equal strides, at the same
+    positions in every array."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"),
+            np.asarray([loss], dtype=np.float64))
+    opt = trainer.opt
+    n = opt.master.numel()
+    idx = None
+    if n > DUMP_MAX_ELEMS:
+        stride = n // DUMP_MAX_ELEMS
+        idx = (np.arange(DUMP_MAX_ELEMS, dtype=np.int64) * stride
+               + np.random.default_rng(0).integers(
+                   0, stride, size=DUMP_MAX_ELEMS))
+        idx = torch.from_numpy(idx).to(opt.master.device)
+    for name, t in (("trainable_params", opt.master), ("adam_m", opt.m),
+                    ("adam_v", opt.v)):
+        t = t.detach()
+        if idx is not None:
+            t = t[idx]
+        np.save(os.path.join(out_dir, name + ".npy"),
+                t.float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -70,9 +113,23 @@ def main():
     ap.add_argument("--grad-ckpt", action="store_true")
     ap.add_argument("--optimizer-mode", default="auto",
                     help="auto | flat | overlap | zero1")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step "
+                         "computed (loss, updated trainable params and "
+                         "AdamW moments) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements and checks "
+                         "(none yet: a plain run already does only "
+                         "setup, warmup, the timed steps and the result "
+                         "line)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
 
     rank, world, local_rank, device = init_distributed()
+    # LoRA dropout draws its per-call kernel seed from torch's global
+    # generator: pin it so equal arguments give equal inputs in every run
+    torch.manual_seed(1234)
     if device.type != "cuda" and args.model == "llama2-7b":
         # CPU smoke fallback keeps the script runnable in the no-GPU
         # container; the measured metric is only valid on MI355X.
@@ -129,6 +186,9 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, trainer)
 
     tokens_per_step = mb * args.seq_len * args.grad_accum * world
     value = tokens_per_step * args.steps / elapsed
