@@ -485,6 +485,11 @@ class FinetuneJobController:
                 # serveConfig.template: chat template for the served
                 # model (llama2 default; llama3 checkpoints need theirs)
                 args += ["--template", str(serve_cfg["template"])]
+            if serve_cfg.get("quantization"):
+                # serveConfig.quantization: serve the base weight-only
+                # quantized (int8/int4), as the job trained against it;
+                # admission rejects it together with tensorParallel > 1
+                args += ["--quantization", str(serve_cfg["quantization"])]
             if ck.get("checkpointPath"):
                 args += ["--adapter", ck["checkpointPath"]]
             base_env = {"PYTHONPATH": self.cfg.repo_root,

@@ -118,7 +118,9 @@ class Finetune(ApiObject):
 
 class FinetuneJob(ApiObject):
     """spec: fineTune{name, finetuneSpec}, scoringPluginConfig{name,
-    parameters}, serveConfig. status: state, finetuneStatus, result{
+    parameters}, serveConfig{tensorParallel, template, quantization
+    (int8|int4, single-GPU serving only)}. status: state,
+    finetuneStatus, result{
     modelExportResult, image, serve, dashboard, score}, stats
     (finetunejob_controller.go:71-143)."""
     kind = "FinetuneJob"

@@ -92,6 +92,14 @@ def validate_(obj: ApiObject) -> None:
                  1 <= tp <= 8,
                  "spec.serveConfig.tensorParallel must be an int in "
                  "[1, 8] (one 8-GPU MI355X node)", errs)
+        quant = sc.get("quantization")
+        if quant is not None:
+            _require(isinstance(quant, str) and quant in ("int8", "int4"),
+                     "spec.serveConfig.quantization must be int8 or int4",
+                     errs)
+            _require(not (isinstance(tp, int) and tp > 1),
+                     "spec.serveConfig.quantization is not supported "
+                     "with tensorParallel > 1", errs)
         tmpl = sc.get("template")
         if tmpl is not None:
             from ..data.templates import TEMPLATES

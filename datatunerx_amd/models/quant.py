@@ -108,18 +108,92 @@ class QuantFrozenLinear(nn.Module):
         return dequantize_int4(self.qweight, self.scale, self.dtype,
                                self.group)
 
+    def _decode_path(self, x) -> bool:
+        """True when the weight-streaming qgemv kernels take this call:
+        a bf16 GPU activation of at most 16 rows that needs no gradient,
+        with a shape inside the kernel contract. Everything else (the
+        quantized training step, prefill, CPU) keeps dequantize +
+        F.linear."""
+        if not (x.is_cuda and x.dtype == torch.bfloat16
+                and self.dtype == torch.bfloat16):
+            return False
+        if torch.is_grad_enabled() and x.requires_grad:
+            return False
+        K = self.in_features
+        if x.shape[-1] != K or x.numel() > 16 * K:
+            return False
+        from ..ops import qlinear_supported
+        return qlinear_supported(x.numel() // K, self.out_features, K,
+                                 self.bits, self.group)
+
     def forward(self, x):
+        if self._decode_path(x):
+            from ..ops import qlinear
+            return qlinear(x.contiguous(), self.qweight, self.scale,
+                           self.bits, self.group)
         return F.linear(x, self.weight)
 
 
+class QuantLoRALinear(QuantFrozenLinear):
+    """Inference-only LoRA projection over a quantized base:
+    y = qlinear(x) + s * (x @ A^T) @ B^T, with lora_A/lora_B kept in the
+    compute dtype. The adapter is NOT merged before quantizing — int4
+    rounding would swallow the low-rank delta the compare service exists
+    to measure. Up to 16 rows run the qgemv kernels; prefill uses the
+    dequantized weight and the same two LoRA ops."""
+
+    def __init__(self, in_features: int, out_features: int, r: int = 8,
+                 alpha: float = 32.0, bits: int = 8,
+                 dtype=torch.bfloat16, group: int = 64):
+        super().__init__(in_features, out_features, bits=bits, dtype=dtype,
+                         group=group)
+        self.r, self.alpha = r, alpha
+        self.lora_scale = alpha / r
+        self.lora_A = nn.Parameter(
+            torch.zeros(r, in_features, dtype=dtype), requires_grad=False)
+        self.lora_B = nn.Parameter(
+            torch.zeros(out_features, r, dtype=dtype), requires_grad=False)
+
+    @classmethod
+    def from_lora(cls, mod, bits: int = 8, group: int = 64):
+        """Build from a LoRALinearModule (base quantized, A/B copied)."""
+        w = mod.weight.detach()
+        with torch.device(w.device):
+            m = cls(mod.in_features, mod.out_features, r=mod.r,
+                    alpha=mod.alpha, bits=bits, dtype=w.dtype, group=group)
+        m.load_weight(w)
+        with torch.no_grad():
+            m.lora_A.copy_(mod.lora_A.detach())
+            m.lora_B.copy_(mod.lora_B.detach())
+        return m
+
+    def forward(self, x):
+        from ..ops import lora_contract, lora_expand_add
+        xs = x.shape
+        x2 = x.reshape(-1, xs[-1])
+        if x2.is_cuda:
+            x2 = x2.contiguous()
+        y = QuantFrozenLinear.forward(self, x2).contiguous()
+        t = lora_contract(x2, self.lora_A)
+        y = lora_expand_add(y, t, self.lora_B, self.lora_scale)
+        return y.reshape(*xs[:-1], self.out_features)
+
+
 @torch.no_grad()
-def quantize_model_(model: nn.Module, bits: int = 8):
-    """Replace every FrozenLinear (and the frozen base weight inside
-    LoRA modules stays bf16 — PEFT quantizes only the base model's
-    nn.Linear layers; our LoRA modules fuse base+adapter, so they are
-    left at bf16 exactly like lm_head fp32-forcing in the reference).
-    Returns the count of quantized layers."""
-    from .lora import FrozenLinear
+def quantize_model_(model: nn.Module, bits: int = 8,
+                    lora_base: bool = False):
+    """Replace every FrozenLinear by a QuantFrozenLinear. By default the
+    frozen base weight inside LoRA modules stays bf16 — PEFT quantizes
+    only the base model's nn.Linear layers; our LoRA modules fuse
+    base+adapter, so they are left at bf16 exactly like lm_head
+    fp32-forcing in the reference — which is what the trainer wants.
+    `lora_base=True` (serving) also replaces every LoRALinearModule by
+    an inference-only QuantLoRALinear holding the quantized base plus
+    the unmerged adapter. Returns the count of quantized layers; raises
+    if there was nothing to quantize."""
+    from .lora import FrozenLinear, LoRALinearModule
+    if bits not in (4, 8):
+        raise ValueError(f"quantize_model_: bits must be 4 or 8, got {bits}")
     n = 0
     for parent in model.modules():
         for name, child in list(parent.named_children()):
@@ -128,4 +202,12 @@ def quantize_model_(model: nn.Module, bits: int = 8):
                     child.weight.detach(), bits=bits)
                 setattr(parent, name, q)
                 n += 1
+            elif lora_base and isinstance(child, LoRALinearModule):
+                setattr(parent, name,
+                        QuantLoRALinear.from_lora(child, bits=bits))
+                n += 1
+    if n == 0:
+        raise ValueError(
+            "quantize_model_: no FrozenLinear/LoRA projection to quantize "
+            f"in {type(model).__name__}")
     return n

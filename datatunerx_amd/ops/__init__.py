@@ -249,6 +249,59 @@ def dequant_int4(packed, scale, group: int = 64):
     return dequantize_int4(packed, scale, torch.bfloat16, group)
 
 
+# ------------------------------------------- quantized decode linear
+QLINEAR_MAX_ROWS = 16
+
+
+def qlinear_supported(M: int, N: int, K: int, bits: int,
+                      group: int = 64) -> bool:
+    """Shapes the weight-streaming qgemv kernels take (qgemv.hip): at
+    most 16 rows, and a K that splits into whole 16-byte weight pieces
+    (each int4 piece inside one scale group). Anything else goes through
+    dequantize-then-linear."""
+    if not (1 <= M <= QLINEAR_MAX_ROWS and N >= 1 and K >= 1):
+        return False
+    if bits == 8:
+        return K % 16 == 0
+    if bits == 4:
+        return K % 32 == 0 and group > 0 and group % 32 == 0 and \
+            K % group == 0
+    return False
+
+
+def qlinear(x, qweight, scale, bits: int, group: int = 64):
+    """y[...,N] = x[...,K] @ dequant(qweight)[N,K]^T for the weight
+    formats of models/quant.py (bits 8: q [N,K] int8 + scale [N];
+    bits 4: packed [N,K/2] uint8 + scale [N,K/group]).
+
+    GPU: the qgemv kernels stream the integer weight and dequantize in
+    registers when the contract holds (bf16 contiguous x, <= 16 rows,
+    qlinear_supported); otherwise the dequant kernel + F.linear. CPU:
+    the fp32 reference."""
+    if bits not in (4, 8):
+        raise ValueError(f"qlinear: bits must be 4 or 8, got {bits}")
+    N = qweight.shape[0]
+    K = qweight.shape[1] * (2 if bits == 4 else 1)
+    if _gpu(x):
+        M = x.numel() // K if K else 0
+        if (x.dtype == torch.bfloat16 and x.shape[-1] == K
+                and x.is_contiguous() and qweight.is_contiguous()
+                and scale.is_contiguous()
+                and qlinear_supported(M, N, K, bits, group)
+                and x.data_ptr() % 16 == 0
+                and qweight.data_ptr() % 16 == 0):
+            if bits == 8:
+                return _EXT.qgemv_int8(x, qweight, scale)
+            return _EXT.qgemv_int4(x, qweight, scale, group)
+        w = (dequant_int8(qweight, scale) if bits == 8
+             else dequant_int4(qweight, scale, group))
+        return torch.nn.functional.linear(x, w.to(x.dtype))
+    from ..models.quant import dequantize_int4, dequantize_int8
+    w = (dequantize_int8(qweight, scale, torch.float32) if bits == 8
+         else dequantize_int4(qweight, scale, torch.float32, group))
+    return (x.float() @ w.t()).to(x.dtype)
+
+
 # ------------------------------------------------------------- AdamW
 def adamw_step(p_bf16, master, grad, m, v, lr, beta1, beta2, eps,
                weight_decay, step: int):

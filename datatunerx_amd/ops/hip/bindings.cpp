@@ -51,6 +51,10 @@ void launch_transpose_sd(const void*, void*, int, int, int, int,
 int attn_decode_nsplit(int Skv);
 void launch_gemv_bf16(const void*, const void*, void*, int, int,
                       hipStream_t);
+void launch_qgemv_int8(const void*, const void*, const float*, void*, int,
+                       int, int, hipStream_t);
+void launch_qgemv_int4(const void*, const void*, const float*, void*, int,
+                       int, int, int, hipStream_t);
 void launch_gemm_nt(const void*, const void*, const void*, void*, long,
                     int, int, hipStream_t);
 void launch_attn_decode(const void*, const void*, const void*,
@@ -443,6 +447,62 @@ torch::Tensor gemv(torch::Tensor x, torch::Tensor w) {
   return y;
 }
 
+// Quantized decode: y[M,N] = x[M,K] @ dequant(Wq)[N,K]^T for M <= 16
+// rows (the flattened leading dims of x), streaming the integer weight
+// (qgemv.hip). Only allocation is the output: hipGraph-capturable.
+static torch::Tensor qgemv_out(const torch::Tensor& x, int N) {
+  auto sizes = x.sizes().vec();
+  sizes[sizes.size() - 1] = N;
+  return torch::empty(sizes, x.options());
+}
+
+static long qgemv_rows(const torch::Tensor& x, int K) {
+  check_bf16_contig(x, "x");
+  TORCH_CHECK(x.dim() >= 1 && x.size(-1) == K, "qgemv: x inner dim != K");
+  const long M = x.numel() / K;
+  TORCH_CHECK(M >= 1 && M <= 16, "qgemv: 1 <= M <= 16, got ", M);
+  TORCH_CHECK((uintptr_t)x.data_ptr() % 16 == 0, "qgemv: x 16-B aligned");
+  return M;
+}
+
+static void qgemv_check_w(const torch::Tensor& w, at::ScalarType dt,
+                          const torch::Tensor& scale, long nscale) {
+  TORCH_CHECK(w.is_cuda() && w.scalar_type() == dt && w.dim() == 2 &&
+              w.is_contiguous(), "qgemv: weight dtype/layout");
+  TORCH_CHECK((uintptr_t)w.data_ptr() % 16 == 0,
+              "qgemv: weight 16-B aligned");
+  TORCH_CHECK(scale.is_cuda() && scale.scalar_type() == torch::kFloat &&
+              scale.is_contiguous() && scale.numel() == nscale,
+              "qgemv: scale dtype/shape");
+}
+
+torch::Tensor qgemv_int8(torch::Tensor x, torch::Tensor q,
+                         torch::Tensor scale) {
+  const int N = (int)q.size(0), K = (int)q.size(1);
+  TORCH_CHECK(K > 0 && K % 16 == 0, "qgemv_int8: K % 16");
+  qgemv_check_w(q, torch::kChar, scale, N);
+  const long M = qgemv_rows(x, K);
+  auto y = qgemv_out(x, N);
+  launch_qgemv_int8(x.data_ptr(), q.data_ptr(), scale.data_ptr<float>(),
+                    y.data_ptr(), (int)M, N, K, cur_stream());
+  return y;
+}
+
+torch::Tensor qgemv_int4(torch::Tensor x, torch::Tensor packed,
+                         torch::Tensor scale, long group) {
+  const int N = (int)packed.size(0), K = (int)packed.size(1) * 2;
+  TORCH_CHECK(K > 0 && K % 32 == 0, "qgemv_int4: K % 32");
+  TORCH_CHECK(group > 0 && group % 32 == 0 && K % group == 0,
+              "qgemv_int4: group % 32, K % group");
+  qgemv_check_w(packed, torch::kByte, scale, (long)N * (K / group));
+  const long M = qgemv_rows(x, K);
+  auto y = qgemv_out(x, N);
+  launch_qgemv_int4(x.data_ptr(), packed.data_ptr(),
+                    scale.data_ptr<float>(), y.data_ptr(), (int)M, N, K,
+                    (int)group, cur_stream());
+  return y;
+}
+
 // Decode fast path: q [B,1,Hq,D] against the KV cache (flash-decoding
 // split-KV partials; no V transpose needed).
 std::vector<torch::Tensor> attn_decode(torch::Tensor q, torch::Tensor k,
@@ -555,6 +615,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_bwd", &attn_bwd);
   m.def("transpose_sd", &transpose_sd);
   m.def("gemv", &gemv);
+  m.def("qgemv_int8", &qgemv_int8, py::arg("x"), py::arg("q"),
+        py::arg("scale"));
+  m.def("qgemv_int4", &qgemv_int4, py::arg("x"), py::arg("packed"),
+        py::arg("scale"), py::arg("group") = 64);
   m.def("gemm_nt", &gemm_nt, py::arg("a"), py::arg("b"),
         py::arg("src") = py::none());
   m.def("attn_decode", &attn_decode, py::arg("q"), py::arg("k"),

@@ -191,8 +191,21 @@ def builtin_config(name: str, **lora_kw):
     raise ValueError(f"unknown model {name!r}")
 
 
+QUANTIZATIONS = {"int8": 8, "int4": 4}
+
+
 def build_model(name: str, device, adapter_dir: Optional[str] = None,
-                lora_kw: Optional[dict] = None):
+                lora_kw: Optional[dict] = None,
+                quantization: Optional[str] = None):
+    """quantization: None | "int8" | "int4" — weight-only quantize every
+    projection (LoRA bases included, adapters kept unmerged in bf16)
+    AFTER weights and adapter are loaded, so the service runs the model
+    a quantized job trained against; decode then streams the integer
+    weights (ops.qlinear) instead of bf16."""
+    if quantization is not None and quantization not in QUANTIZATIONS:
+        raise ValueError(
+            f"unknown quantization {quantization!r} "
+            f"(expected one of {sorted(QUANTIZATIONS)})")
     dtype = torch.bfloat16 if device.type == "cuda" else torch.float32
     lora_kw = dict(lora_kw or {})
     if adapter_dir and not lora_kw:
@@ -226,6 +239,13 @@ def build_model(name: str, device, adapter_dir: Optional[str] = None,
         model.init_random()      # builtin names: random-init (no network)
     if adapter_dir:
         load_adapter(model, adapter_dir)
+    if quantization is not None:
+        if not isinstance(model, LlamaForCausalLM):
+            raise ValueError(
+                f"quantized serving supports llama models, not {name!r} "
+                "(its layers are not FrozenLinear)")
+        from ..models.quant import quantize_model_
+        quantize_model_(model, QUANTIZATIONS[quantization], lora_base=True)
     model.eval()
     return model
 

@@ -405,18 +405,49 @@ def _llama_config(name: str):
     return cfg
 
 
-def main(argv=None):
-    import os
-
-    from .engine import InferenceEngine, build_model
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--port", type=int, default=8000)
     ap.add_argument("--host", default="127.0.0.1")
     ap.add_argument("--model", default="llama2-7b")
     ap.add_argument("--adapter", default=None)
     ap.add_argument("--template", default="llama2")
-    args = ap.parse_args(argv)
+    ap.add_argument("--quantization", choices=("int8", "int4"),
+                    default=None,
+                    help="serve the base weights weight-only quantized "
+                         "(adapters stay bf16, unmerged); single-GPU "
+                         "llama models only")
+    return ap.parse_args(argv)
+
+
+def _check_quantization(args, world: int):
+    """--quantization is refused at start-up where it cannot be honoured
+    rather than silently serving bf16."""
+    if not args.quantization:
+        return
+    if world > 1:
+        raise SystemExit(
+            "--quantization is not supported with tensor-parallel serving "
+            f"(WORLD_SIZE={world}); serve quantized models on one GPU")
+    from .engine import builtin_config
+    from ..models.hf_io import is_hf_model_dir
+    if not is_hf_model_dir(args.model):
+        try:
+            family, _ = builtin_config(args.model)
+        except ValueError as e:
+            raise SystemExit(str(e))
+        if family != "llama":
+            raise SystemExit(
+                f"--quantization supports llama models, not {args.model!r}")
+
+
+def main(argv=None):
+    import os
+
+    from .engine import InferenceEngine, build_model
+    args = parse_args(argv)
     world = int(os.environ.get("WORLD_SIZE", "1"))
+    _check_quantization(args, world)
     if world > 1:
         # tensor-parallel service (launched under torchrun, 1 rank/GPU):
         # rank 0 serves HTTP; followers run the collectives in lockstep.
@@ -472,7 +503,8 @@ def main(argv=None):
     from ..models import LlamaForCausalLM
     from ..models.hf_io import load_tokenizer
     device = torch.device("cuda:0" if torch.cuda.is_available() else "cpu")
-    model = build_model(args.model, device, adapter_dir=args.adapter)
+    model = build_model(args.model, device, adapter_dir=args.adapter,
+                        quantization=args.quantization)
     tok = load_tokenizer(args.model)
     n_slots = max(1, int(os.environ.get("DTX_SERVE_CONCURRENCY", "2")))
     pool = EnginePool([
