@@ -21,6 +21,7 @@ from ..ops.autograd import (PairedFrozenGemm, QKVProj, attention,
                             cross_entropy, rmsnorm, rmsnorm_tap,
                             rope, swiglu)
 from .lora import FrozenLinear, LoRALinearModule
+from .multilora import MultiLoRALinear
 
 
 @dataclass
@@ -98,6 +99,16 @@ class LlamaConfig:
         return cls(**d)
 
 
+def _mproj(mod, x, adapters, residual=None):
+    """Call a projection, handing the per-request adapter selection
+    (multi-adapter serving) only to the modules that hold an adapter
+    stack; every other module is called exactly as without it."""
+    if adapters is not None and isinstance(mod, MultiLoRALinear):
+        return mod(x, adapters=adapters, residual=residual)
+    y = mod(x)
+    return y if residual is None else residual + y
+
+
 def _proj(cfg: LlamaConfig, name: str, in_f: int, out_f: int, lora: bool,
           dtype):
     if lora and name in cfg.lora_targets:
@@ -157,7 +168,7 @@ class LlamaAttention(nn.Module):
                 qm.dropout == vm.dropout)
 
     def forward(self, x, cos, sin, pos0: int = 0, kv_cache=None,
-                pos_dev=None, residual=None):
+                pos_dev=None, residual=None, adapters=None):
         B, S, _ = x.shape
         cfg = self.cfg
         H, Hkv, D = cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim
@@ -172,9 +183,9 @@ class LlamaAttention(nn.Module):
                                     km.weight, vm.weight, vm.lora_A,
                                     vm.lora_B, qm.scale, sq, sv, keep)
         else:
-            q = self.q_proj(x)
-            k = self.k_proj(x)
-            v = self.v_proj(x)
+            q = _mproj(self.q_proj, x, adapters)
+            k = _mproj(self.k_proj, x, adapters)
+            v = _mproj(self.v_proj, x, adapters)
         if self.q_bias is not None:
             q = q + self.q_bias
             k = k + self.k_bias
@@ -194,8 +205,7 @@ class LlamaAttention(nn.Module):
         o = o.reshape(B, S, H * D)
         if residual is not None and isinstance(self.o_proj, FrozenLinear):
             return self.o_proj(o, residual)   # residual in GEMM epilogue
-        y = self.o_proj(o)
-        return y if residual is None else residual + y
+        return _mproj(self.o_proj, o, adapters, residual)
 
 
 class LlamaMLP(nn.Module):
@@ -208,7 +218,7 @@ class LlamaMLP(nn.Module):
         self.down_proj = _proj(cfg, "down_proj", cfg.intermediate_size,
                                cfg.hidden_size, lora, dtype)
 
-    def forward(self, x, residual=None):
+    def forward(self, x, residual=None, adapters=None):
         if type(self.gate_proj) is FrozenLinear and \
                 type(self.up_proj) is FrozenLinear and \
                 not self.gate_proj.weight.requires_grad:
@@ -218,11 +228,11 @@ class LlamaMLP(nn.Module):
                                           self.up_proj.weight)
             h = swiglu(g, u)
         else:
-            h = swiglu(self.gate_proj(x), self.up_proj(x))
+            h = swiglu(_mproj(self.gate_proj, x, adapters),
+                       _mproj(self.up_proj, x, adapters))
         if residual is not None and isinstance(self.down_proj, FrozenLinear):
             return self.down_proj(h, residual)    # residual in epilogue
-        y = self.down_proj(h)
-        return y if residual is None else residual + y
+        return _mproj(self.down_proj, h, adapters, residual)
 
 
 class LlamaDecoderLayer(nn.Module):
@@ -237,14 +247,20 @@ class LlamaDecoderLayer(nn.Module):
         self.mlp = LlamaMLP(cfg, lora, dtype)
 
     def forward(self, x, cos, sin, pos0: int = 0, kv_cache=None,
-                pos_dev=None):
+                pos_dev=None, adapters=None):
         h, res = rmsnorm_tap(x, self.input_layernorm,
                              self.cfg.rms_norm_eps)
-        x = self.self_attn(h, cos, sin, pos0, kv_cache, pos_dev,
-                           residual=res)
+        if adapters is None:
+            x = self.self_attn(h, cos, sin, pos0, kv_cache, pos_dev,
+                               residual=res)
+        else:
+            x = self.self_attn(h, cos, sin, pos0, kv_cache, pos_dev,
+                               residual=res, adapters=adapters)
         h, res = rmsnorm_tap(x, self.post_attention_layernorm,
                              self.cfg.rms_norm_eps)
-        return self.mlp(h, residual=res)
+        if adapters is None:
+            return self.mlp(h, residual=res)
+        return self.mlp(h, residual=res, adapters=adapters)
 
 
 class LlamaForCausalLM(nn.Module):
@@ -291,7 +307,7 @@ class LlamaForCausalLM(nn.Module):
         return self
 
     def hidden_states(self, input_ids, pos0: int = 0, kv_caches=None,
-                      pos_dev=None):
+                      pos_dev=None, adapters=None):
         x = self.embed_tokens(input_ids)
         cos, sin = self.rope_cos, self.rope_sin
         for i, layer in enumerate(self.layers):
@@ -299,15 +315,21 @@ class LlamaForCausalLM(nn.Module):
             if self.cfg.gradient_checkpointing and self.training:
                 x = torch.utils.checkpoint.checkpoint(
                     layer, x, cos, sin, pos0, cache, use_reentrant=False)
+            elif adapters is not None:
+                x = layer(x, cos, sin, pos0, cache, pos_dev,
+                          adapters=adapters)
             else:
                 x = layer(x, cos, sin, pos0, cache, pos_dev)
         return rmsnorm(x, self.norm, self.cfg.rms_norm_eps)
 
     def forward(self, input_ids, labels=None, pos0: int = 0,
-                kv_caches=None, pos_dev=None):
+                kv_caches=None, pos_dev=None, adapters=None):
         """Returns loss (if labels given, shifted CE with -100 ignore)
-        else logits."""
-        h = self.hidden_states(input_ids, pos0, kv_caches, pos_dev)
+        else logits. adapters: per-sequence adapter selection for a
+        model with attached adapter stacks (models/multilora.py); None
+        runs the base model."""
+        h = self.hidden_states(input_ids, pos0, kv_caches, pos_dev,
+                               adapters)
         if labels is None:
             return self.lm_head(h)
         if os.environ.get("DTX_FUSED_CE") == "1" and \

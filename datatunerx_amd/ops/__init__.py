@@ -235,6 +235,59 @@ def dropout_mask(M: int, K: int, seed: int, keep: float, like):
                             dtype=torch.bfloat16)
 
 
+# ------------------------------------------- multi-adapter decode LoRA
+MLORA_MAX_ROWS = 16
+MLORA_RANKS = (8, 16, 32, 64)
+
+
+def mlora_supported(M: int, N: int, K: int, R: int) -> bool:
+    """Shapes the gathered LoRA kernels take (mlora.hip): at most 16
+    decode rows, K and N in whole 16-byte bf16 pieces, and a stack rank
+    of 8, 16, 32 or 64 (smaller ranks are zero-padded into the stack)."""
+    return (1 <= M <= MLORA_MAX_ROWS and K >= 8 and K % 8 == 0
+            and N >= 8 and N % 8 == 0 and R in MLORA_RANKS)
+
+
+def mlora_add(y, x, A, Bt, scale, idx):
+    """In place on y [M,N]: y[m] += scale[g] * (x[m] @ A[g]^T) @ Bt[g]
+    with g = idx[m]; rows with idx outside [0,G) keep their bits.
+    A [G,R,K], Bt [G,R,N] (B pre-transposed), scale [G] f32, idx [M]
+    int32 on y's device. On the GPU idx is read by the kernels only (no
+    host sync: hipGraph-capturable). There is no fallback in here:
+    callers check mlora_supported first, anything else raises."""
+    if not (y.dim() == 2 and x.dim() == 2 and A.dim() == 3
+            and Bt.dim() == 3):
+        raise ValueError("mlora_add: y [M,N], x [M,K], A [G,R,K], "
+                         "Bt [G,R,N]")
+    M, K = x.shape
+    N = y.shape[1]
+    G, R = A.shape[0], A.shape[1]
+    if not (y.shape[0] == M and A.shape[2] == K
+            and tuple(Bt.shape) == (G, R, N) and scale.numel() == G
+            and idx.numel() == M):
+        raise ValueError(
+            f"mlora_add: shape mismatch (y {tuple(y.shape)}, x "
+            f"{tuple(x.shape)}, A {tuple(A.shape)}, Bt {tuple(Bt.shape)}, "
+            f"scale {tuple(scale.shape)}, idx {tuple(idx.shape)})")
+    if not mlora_supported(M, N, K, R):
+        raise ValueError(
+            f"mlora_add: M={M} N={N} K={K} R={R} is outside the kernel "
+            "contract (see mlora_supported)")
+    if _gpu(y):
+        if not (y.dtype == x.dtype == A.dtype == Bt.dtype == torch.bfloat16
+                and scale.dtype == torch.float32
+                and idx.dtype == torch.int32 and idx.is_cuda
+                and all(t.is_contiguous() and t.data_ptr() % 16 == 0
+                        for t in (y, x, A, Bt))
+                and scale.is_contiguous() and idx.is_contiguous()):
+            raise ValueError(
+                "mlora_add: GPU tensors must be contiguous 16-byte-aligned "
+                "bf16 (y, x, A, Bt), f32 scale and int32 device idx")
+        _EXT.mlora_add(y, x, A, Bt, scale, idx)
+        return y
+    return ref.mlora_add(y, x, A, Bt, scale, idx)
+
+
 # -------------------------------------------------- weight dequant
 def dequant_int8(q, scale):
     if _gpu(q):

@@ -55,6 +55,10 @@ void launch_qgemv_int8(const void*, const void*, const float*, void*, int,
                        int, int, hipStream_t);
 void launch_qgemv_int4(const void*, const void*, const float*, void*, int,
                        int, int, int, hipStream_t);
+void launch_mlora_shrink(const void*, const void*, const int*, float*, int,
+                         int, int, int, hipStream_t);
+void launch_mlora_expand_add(void*, const float*, const void*, const float*,
+                             const int*, int, int, int, int, hipStream_t);
 void launch_gemm_nt(const void*, const void*, const void*, void*, long,
                     int, int, hipStream_t);
 void launch_attn_decode(const void*, const void*, const void*,
@@ -503,6 +507,50 @@ torch::Tensor qgemv_int4(torch::Tensor x, torch::Tensor packed,
   return y;
 }
 
+// Multi-adapter decode: y[m] += scale[g] * (x[m] @ A[g]^T) @ Bt[g] with
+// g = idx[m] read ON THE DEVICE (mlora.hip); rows with an index outside
+// [0,G) are left untouched. Nothing here looks at idx's content and the
+// only allocation is t, so the call is hipGraph-capturable and a replay
+// follows whatever idx holds by then.
+void mlora_add(torch::Tensor y, torch::Tensor x, torch::Tensor A,
+               torch::Tensor Bt, torch::Tensor scale, torch::Tensor idx) {
+  check_bf16_contig(y, "y");
+  check_bf16_contig(x, "x");
+  check_bf16_contig(A, "A");
+  check_bf16_contig(Bt, "Bt");
+  TORCH_CHECK(y.dim() == 2 && x.dim() == 2 && A.dim() == 3 && Bt.dim() == 3,
+              "mlora: y [M,N], x [M,K], A [G,R,K], Bt [G,R,N]");
+  const long M = x.size(0), K = x.size(1), N = y.size(1);
+  const long G = A.size(0), R = A.size(1);
+  TORCH_CHECK(y.size(0) == M, "mlora: y/x rows differ");
+  TORCH_CHECK(A.size(2) == K && Bt.size(0) == G && Bt.size(1) == R &&
+              Bt.size(2) == N, "mlora: A [G,R,K] / Bt [G,R,N] mismatch");
+  TORCH_CHECK(M >= 1 && M <= 16, "mlora: 1 <= M <= 16, got ", M);
+  TORCH_CHECK(K >= 8 && K % 8 == 0 && N >= 8 && N % 8 == 0,
+              "mlora: K % 8, N % 8");
+  TORCH_CHECK(R == 8 || R == 16 || R == 32 || R == 64,
+              "mlora: R must be 8, 16, 32 or 64, got ", R);
+  TORCH_CHECK(G >= 1 && G * R * std::max(K, N) < (1L << 40),
+              "mlora: stack size");
+  TORCH_CHECK(scale.is_cuda() && scale.scalar_type() == torch::kFloat &&
+              scale.is_contiguous() && scale.numel() == G,
+              "mlora: scale must be f32 [G] on the GPU");
+  TORCH_CHECK(idx.is_cuda() && idx.scalar_type() == torch::kInt &&
+              idx.is_contiguous() && idx.numel() == M,
+              "mlora: idx must be int32 [M] on the GPU");
+  TORCH_CHECK((uintptr_t)y.data_ptr() % 16 == 0 &&
+              (uintptr_t)x.data_ptr() % 16 == 0 &&
+              (uintptr_t)A.data_ptr() % 16 == 0 &&
+              (uintptr_t)Bt.data_ptr() % 16 == 0, "mlora: 16-B alignment");
+  auto t = torch::empty({M, R}, x.options().dtype(torch::kFloat));
+  launch_mlora_shrink(x.data_ptr(), A.data_ptr(), idx.data_ptr<int>(),
+                      t.data_ptr<float>(), (int)M, (int)K, (int)R, (int)G,
+                      cur_stream());
+  launch_mlora_expand_add(y.data_ptr(), t.data_ptr<float>(), Bt.data_ptr(),
+                          scale.data_ptr<float>(), idx.data_ptr<int>(),
+                          (int)M, (int)N, (int)R, (int)G, cur_stream());
+}
+
 // Decode fast path: q [B,1,Hq,D] against the KV cache (flash-decoding
 // split-KV partials; no V transpose needed).
 std::vector<torch::Tensor> attn_decode(torch::Tensor q, torch::Tensor k,
@@ -619,6 +667,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("scale"));
   m.def("qgemv_int4", &qgemv_int4, py::arg("x"), py::arg("packed"),
         py::arg("scale"), py::arg("group") = 64);
+  m.def("mlora_add", &mlora_add, py::arg("y"), py::arg("x"), py::arg("A"),
+        py::arg("Bt"), py::arg("scale"), py::arg("idx"));
   m.def("gemm_nt", &gemm_nt, py::arg("a"), py::arg("b"),
         py::arg("src") = py::none());
   m.def("attn_decode", &attn_decode, py::arg("q"), py::arg("k"),

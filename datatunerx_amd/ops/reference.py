@@ -265,6 +265,21 @@ def lora_expand_add(y: torch.Tensor, t: torch.Tensor, w: torch.Tensor,
     return y
 
 
+def mlora_add(y: torch.Tensor, x: torch.Tensor, A: torch.Tensor,
+              Bt: torch.Tensor, scale: torch.Tensor, idx: torch.Tensor):
+    """Per-row gathered LoRA update, in place on y [M,N]:
+    y[m] += scale[g] * (x[m] @ A[g]^T) @ Bt[g] with g = idx[m]; rows
+    whose index is outside [0,G) are left untouched. A [G,R,K],
+    Bt [G,R,N] (B pre-transposed), scale [G] f32, idx [M] int."""
+    G = A.shape[0]
+    for m, g in enumerate(idx.tolist()):
+        if 0 <= g < G:
+            t = x[m].float() @ A[g].float().t()                  # [R]
+            d = float(scale[g]) * (t @ Bt[g].float())            # [N]
+            y[m] = (y[m].float() + d).to(y.dtype)
+    return y
+
+
 def lora_wgrad(t: torch.Tensor, x: torch.Tensor, scale: float = 1.0,
                mask=None, seed: int = 0, keep: float = 1.0):
     """dW[r,K] = scale * t[M,r]^T @ (x o mask)[M,K]  (fp32)."""

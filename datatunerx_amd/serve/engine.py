@@ -80,22 +80,31 @@ class _BatchedGraphedDecoder:
             for _ in range(cfg.num_hidden_layers)]
         self.input = torch.ones(B, 1, dtype=torch.long, device=device)
         self.model = model
+        # multi-adapter models: the adapter of each row lives in a
+        # device buffer the captured kernels read at replay, so ONE
+        # graph serves every assignment (-1 = base / dummy row)
+        self.adapter_idx, akw = _graph_adapter_buffer(model, B, device)
         with torch.no_grad():
             for _ in range(3):
                 lg = model(self.input, pos_dev=self.pos32,
-                           kv_caches=self.caches)
+                           kv_caches=self.caches, **akw)
                 lg[:, -1].argmax(-1)
             torch.cuda.synchronize()
             self.graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.graph):
                 lg = model(self.input, pos_dev=self.pos32,
-                           kv_caches=self.caches)
+                           kv_caches=self.caches, **akw)
                 self.out = lg[:, -1].argmax(-1)
 
     def reset(self):
         self.pos64.zero_()
         self.pos32.zero_()
         self.len32.zero_()
+
+    def set_adapters(self, idx):
+        """idx: one adapter index per row of the padded batch."""
+        if self.adapter_idx is not None:
+            self.adapter_idx.copy_(torch.tensor(idx, dtype=torch.int32))
 
     def set_state(self, lens):
         pos = torch.tensor(lens, dtype=torch.long,
@@ -194,14 +203,37 @@ def builtin_config(name: str, **lora_kw):
 QUANTIZATIONS = {"int8": 8, "int4": 4}
 
 
+def _graph_adapter_buffer(model, rows: int, device):
+    """(int32 [rows] index buffer filled with -1, model kwargs) for a
+    graphed decoder over a multi-adapter model; (None, {}) otherwise —
+    such a model captures exactly as before."""
+    if getattr(model, "adapters", None) is None:
+        return None, {}
+    from ..models.multilora import AdapterSelection
+    buf = torch.full((rows,), -1, dtype=torch.int32, device=device)
+    return buf, {"adapters": AdapterSelection(buf, None)}
+
+
 def build_model(name: str, device, adapter_dir: Optional[str] = None,
                 lora_kw: Optional[dict] = None,
-                quantization: Optional[str] = None):
+                quantization: Optional[str] = None,
+                adapters: Optional[dict] = None):
     """quantization: None | "int8" | "int4" — weight-only quantize every
     projection (LoRA bases included, adapters kept unmerged in bf16)
     AFTER weights and adapter are loaded, so the service runs the model
     a quantized job trained against; decode then streams the integer
-    weights (ops.qlinear) instead of bf16."""
+    weights (ops.qlinear) instead of bf16.
+
+    adapters: {name: adapter_dir, ...} — multi-adapter serving: the
+    model is built WITHOUT LoRA modules and every targeted projection
+    gets a stack of all the adapters (models/multilora.py); the name ->
+    index registry hangs on the model as `model.adapters` and requests
+    pick an adapter by name. Mutually exclusive with adapter_dir."""
+    if adapters is not None and adapter_dir:
+        raise ValueError("build_model: give either adapter_dir (one "
+                         "adapter) or adapters (named stack), not both")
+    if adapters is not None and not adapters:
+        raise ValueError("build_model: adapters is empty")
     if quantization is not None and quantization not in QUANTIZATIONS:
         raise ValueError(
             f"unknown quantization {quantization!r} "
@@ -229,7 +261,13 @@ def build_model(name: str, device, adapter_dir: Optional[str] = None,
                                      lora=bool(adapter_dir), dtype=dtype)
         else:
             family, cfg = builtin_config(name, **lora_kw)
-            if family == "llama":
+            if adapters is not None and family != "llama":
+                raise ValueError(
+                    f"multi-adapter serving supports llama models, not "
+                    f"{name!r}")
+            if family == "llama" and adapters is not None:
+                model = LlamaForCausalLM(cfg, lora=False, dtype=dtype)
+            elif family == "llama":
                 model = LlamaForCausalLM(cfg, dtype=dtype)
             else:
                 model = GPT2ForCausalLM(cfg, dtype=dtype)
@@ -239,6 +277,9 @@ def build_model(name: str, device, adapter_dir: Optional[str] = None,
         model.init_random()      # builtin names: random-init (no network)
     if adapter_dir:
         load_adapter(model, adapter_dir)
+    if adapters is not None:
+        from ..models.multilora import attach_adapters_
+        attach_adapters_(model, adapters)
     if quantization is not None:
         if not isinstance(model, LlamaForCausalLM):
             raise ValueError(
@@ -269,17 +310,18 @@ class _GraphedDecoder:
                     graph_len=self.len32)
             for _ in range(cfg.num_hidden_layers)]
         self.input_id = torch.zeros(1, 1, dtype=torch.long, device=device)
+        self.adapter_idx, akw = _graph_adapter_buffer(model, 1, device)
         # warmup (allocator + kernels), then capture
         with torch.no_grad():
             for _ in range(3):
                 self.model(self.input_id, pos_dev=self.pos32,
-                           kv_caches=self.caches)
+                           kv_caches=self.caches, **akw)
             torch.cuda.synchronize()
             self.graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.graph):
                 self.logits = self.model(self.input_id,
                                          pos_dev=self.pos32,
-                                         kv_caches=self.caches)
+                                         kv_caches=self.caches, **akw)
 
     def reset(self):
         self.pos64.zero_()
@@ -287,6 +329,10 @@ class _GraphedDecoder:
         self.len32.fill_(1)
         for c in self.caches:
             c.cur = 0
+
+    def set_adapter(self, g: int):
+        if self.adapter_idx is not None:
+            self.adapter_idx.copy_(torch.tensor([g], dtype=torch.int32))
 
     def after_prefill(self, n: int):
         """counters for the first graphed token (written at index n)."""
@@ -353,6 +399,30 @@ class InferenceEngine:
         except (KeyError, TypeError):
             pass
 
+    # ---------------------------------------------------- adapters
+    def _adapter_index(self, adapter: Optional[str]) -> int:
+        """Registry index of a request's adapter (-1: base model).
+        Raises ValueError for a name the model does not hold — before
+        any GPU work of the request."""
+        if adapter is None:
+            return -1
+        reg = getattr(self.model, "adapters", None)
+        if reg is None:
+            raise ValueError(
+                f"unknown adapter {adapter!r}: this model was built "
+                "without named adapters")
+        return reg.index(adapter)
+
+    def _selection(self, idx):
+        """Model kwargs for per-sequence adapter indices: {} when every
+        sequence runs the base model."""
+        if all(g < 0 for g in idx):
+            return {}
+        from ..models.multilora import AdapterSelection
+        return {"adapters": AdapterSelection(
+            torch.tensor(list(idx), dtype=torch.int32,
+                         device=self.device), idx)}
+
     def _is_stop(self, tok_id) -> bool:
         return int(tok_id) in self._stop_ids
 
@@ -392,13 +462,18 @@ class InferenceEngine:
 
     # ------------------------------------------------------------ chat
     def chat(self, messages: List[dict], max_tokens: int = 64,
-             temperature: float = 0.0, top_p: float = 1.0) -> str:
-        """messages: [{role, content}] -> completion text."""
+             temperature: float = 0.0, top_p: float = 1.0,
+             adapter: Optional[str] = None) -> str:
+        """messages: [{role, content}] -> completion text. adapter: name
+        of an attached adapter (None: the base model)."""
+        self._adapter_index(adapter)
         with self._stream_ctx():
-            return self._chat(messages, max_tokens, temperature, top_p)
+            return self._chat(messages, max_tokens, temperature, top_p,
+                              adapter)
 
     def _chat(self, messages: List[dict], max_tokens: int = 64,
-              temperature: float = 0.0, top_p: float = 1.0) -> str:
+              temperature: float = 0.0, top_p: float = 1.0,
+              adapter: Optional[str] = None) -> str:
         system = ""
         history = []
         query = ""
@@ -414,17 +489,20 @@ class InferenceEngine:
         query = pending_user or ""
         t = get_template(self.template)
         src, _ = t.encode_oneturn(self.tok, query, "", history, system)
-        ids = self.generate(src, max_tokens, temperature, top_p)
+        ids = self.generate(src, max_tokens, temperature, top_p,
+                            adapter=adapter)
         return self.tok.decode(ids)
 
     def chat_stream(self, messages: List[dict], max_tokens: int = 64,
-                    temperature: float = 0.0, top_p: float = 1.0):
+                    temperature: float = 0.0, top_p: float = 1.0,
+                    adapter: Optional[str] = None):
+        self._adapter_index(adapter)
         for delta in self._chat_stream_inner(messages, max_tokens,
-                                             temperature, top_p):
+                                             temperature, top_p, adapter):
             yield delta
 
     def _chat_stream_inner(self, messages, max_tokens, temperature,
-                           top_p):
+                           top_p, adapter=None):
         """Like chat() but yields text DELTAS as tokens decode (the
         serving endpoint streams these as SSE chunks). Token-identical
         to chat(): same generate loop, so TP followers running chat()
@@ -443,7 +521,7 @@ class InferenceEngine:
                                   history, system)
         ids, sent = [], ""
         for tok_id in self.generate_stream(src, max_tokens, temperature,
-                                           top_p):
+                                           top_p, adapter=adapter):
             ids.append(tok_id)
             full = self.tok.decode(ids)
             # hold back trailing U+FFFD: a multi-byte UTF-8 char split
@@ -462,24 +540,29 @@ class InferenceEngine:
 
     @torch.no_grad()
     def generate(self, prompt_ids: List[int], max_new_tokens: int = 64,
-                 temperature: float = 0.0, top_p: float = 1.0) -> List[int]:
+                 temperature: float = 0.0, top_p: float = 1.0,
+                 adapter: Optional[str] = None) -> List[int]:
         return list(self.generate_stream(prompt_ids, max_new_tokens,
-                                         temperature, top_p))
+                                         temperature, top_p,
+                                         adapter=adapter))
 
     @torch.no_grad()
     def generate_stream(self, prompt_ids: List[int],
                         max_new_tokens: int = 64, temperature: float = 0.0,
-                        top_p: float = 1.0):
+                        top_p: float = 1.0, adapter: Optional[str] = None):
+        gi = self._adapter_index(adapter)
         with self._stream_ctx():
             yield from self._generate_stream(prompt_ids, max_new_tokens,
-                                             temperature, top_p)
+                                             temperature, top_p, gi)
 
     @torch.no_grad()
     def _generate_stream(self, prompt_ids: List[int],
                          max_new_tokens: int = 64,
-                         temperature: float = 0.0, top_p: float = 1.0):
+                         temperature: float = 0.0, top_p: float = 1.0,
+                         gi: int = -1):
         if not prompt_ids:
             raise ValueError("empty prompt")
+        akw = self._selection([gi])
         limit = getattr(self.model.cfg, "max_position_embeddings", 1 << 30)
         if len(prompt_ids) >= limit:
             raise ValueError(
@@ -494,7 +577,8 @@ class InferenceEngine:
             # hipGraph-replayed decode: prefill eagerly into the graph's
             # caches, then one graph replay per token
             gd.reset()
-            logits = self.model(ids, pos0=0, kv_caches=gd.caches)
+            gd.set_adapter(gi)
+            logits = self.model(ids, pos0=0, kv_caches=gd.caches, **akw)
             gd.after_prefill(len(prompt_ids))
             nxt = self._sample(logits[0, -1], temperature, top_p)
             for _ in range(max_new_tokens):
@@ -518,7 +602,8 @@ class InferenceEngine:
             pos = 0
             cur = ids
             for _ in range(max_new_tokens):
-                logits = self.model(cur, pos0=pos, kv_caches=caches)
+                logits = self.model(cur, pos0=pos, kv_caches=caches,
+                                    **akw)
                 pos += cur.shape[1]
                 if pos >= max_s:
                     break
@@ -574,13 +659,26 @@ class InferenceEngine:
     def generate_batch(self, prompts: List[List[int]],
                        max_new_tokens: int = 64,
                        temperature: float = 0.0,
-                       top_p: float = 1.0) -> List[List[int]]:
+                       top_p: float = 1.0,
+                       adapters: Optional[List[Optional[str]]] = None
+                       ) -> List[List[int]]:
         """Ragged batched generation: per-row prefill, then ONE decode
         step per token for the whole batch (the weight stream is read
-        once per step instead of once per request)."""
+        once per step instead of once per request). adapters: one
+        adapter name (or None: base model) per prompt — rows of one
+        batch may use different adapters."""
+        self._adapter_indices(adapters, len(prompts))
         with self._stream_ctx():
             return self._generate_batch(prompts, max_new_tokens,
-                                        temperature, top_p)
+                                        temperature, top_p,
+                                        adapters=adapters)
+
+    def _adapter_indices(self, adapters, n: int):
+        if adapters is None:
+            return [-1] * n
+        if len(adapters) != n:
+            raise ValueError(f"{len(adapters)} adapters for {n} prompts")
+        return [self._adapter_index(a) for a in adapters]
 
     def _get_batched_graphed(self, max_s):
         if self._bgraphed is None and self._graph_ok:
@@ -595,21 +693,24 @@ class InferenceEngine:
 
     @torch.no_grad()
     def _generate_batch(self, prompts, max_new_tokens, temperature,
-                        top_p, budgets=None):
+                        top_p, budgets=None, adapters=None):
         outs = [[] for _ in prompts]
         for emitted in self._generate_batch_steps(
-                prompts, max_new_tokens, temperature, top_p, budgets):
+                prompts, max_new_tokens, temperature, top_p, budgets,
+                adapters):
             for i, t in emitted:
                 outs[i].append(t)
         return outs
 
     @torch.no_grad()
     def _generate_batch_steps(self, prompts, max_new_tokens, temperature,
-                              top_p, budgets=None):
+                              top_p, budgets=None, adapters=None):
         """Yields, per decode step, the [(row, token)] emissions.
         budgets: optional per-row max_tokens (rows stop emitting — and
-        count as done — at their own budget)."""
+        count as done — at their own budget). adapters: optional
+        per-row adapter names."""
         assert self.is_llama, "batched decode is the Llama path"
+        aidx = self._adapter_indices(adapters, len(prompts))
         cfg = self.model.cfg
         greedy = not (temperature and temperature > 0)
         lens0 = [len(p) for p in prompts]
@@ -627,6 +728,8 @@ class InferenceEngine:
             prompts = list(prompts) + \
                 [[self.tok.bos_token_id]] * (gd.B - len(prompts))
         B = len(prompts)
+        aidx = aidx + [-1] * (B - len(aidx))     # dummy rows: base
+        akw = self._selection(aidx)
         lens = [len(p) for p in prompts]
         max_s = gd.max_s if gd is not None else min(
             cfg.max_position_embeddings,
@@ -636,6 +739,7 @@ class InferenceEngine:
             # no cache zeroing needed: prefill overwrites rows up to
             # len and attention never reads past len32
             gd.reset()
+            gd.set_adapters(aidx)
             caches = gd.caches
         else:
             caches = [BatchedKVCache(B, cfg.num_key_value_heads, max_s,
@@ -651,7 +755,7 @@ class InferenceEngine:
             for i, ids in enumerate(prompts):
                 padded[i, :len(ids)] = torch.tensor(ids,
                                                     dtype=torch.long)
-            logits = self.model(padded, pos0=0, kv_caches=caches)
+            logits = self.model(padded, pos0=0, kv_caches=caches, **akw)
             for i in range(B):
                 nxt[i] = self._sample(logits[i, lens[i] - 1],
                                       temperature, top_p)
@@ -660,7 +764,8 @@ class InferenceEngine:
                 row = [c.row_view(i) for c in caches]
                 t = torch.tensor([ids], dtype=torch.long,
                                  device=self.device)
-                logits = self.model(t, pos0=0, kv_caches=row)
+                logits = self.model(t, pos0=0, kv_caches=row,
+                                    **self._selection([aidx[i]]))
                 nxt[i] = self._sample(logits[0, -1], temperature, top_p)
         pos = torch.tensor(lens, dtype=torch.long, device=self.device)
         if gd is not None:
@@ -699,7 +804,8 @@ class InferenceEngine:
                 toks = out.tolist()
                 cur = out.view(B, 1)
             else:
-                logits = self.model(cur, kv_caches=caches, pos_dev=p32)
+                logits = self.model(cur, kv_caches=caches, pos_dev=p32,
+                                    **akw)
                 for c in caches:
                     c.pos64 += 1
                     c.len32 += 1
@@ -752,13 +858,25 @@ class InferenceEngine:
                                  "temperature/top_p")
         return prompts, budgets, temp, top_p
 
+    def _request_adapters(self, requests):
+        """Per-request "adapter" names (None when no request names one);
+        unknown names raise ValueError here, before the generation."""
+        names = [r.get("adapter") for r in requests]
+        if all(n is None for n in names):
+            return None
+        self._adapter_indices(names, len(names))
+        return names
+
     def chat_batch(self, requests: List[dict]) -> List[str]:
-        """requests: [{messages, max_tokens, temperature, top_p}] ->
-        completion texts (one batched generation)."""
+        """requests: [{messages, max_tokens, temperature, top_p,
+        adapter}] -> completion texts (one batched generation; the
+        optional "adapter" is chosen per request)."""
         prompts, budgets, temp, top_p = self._encode_requests(requests)
+        names = self._request_adapters(requests)
         with self._stream_ctx():
             outs = self._generate_batch(prompts, max(budgets), temp,
-                                        top_p, budgets=budgets)
+                                        top_p, budgets=budgets,
+                                        adapters=names)
         return [self.tok.decode(o) for o in outs]
 
     def chat_batch_stream(self, requests: List[dict]):
@@ -767,13 +885,15 @@ class InferenceEngine:
         Deltas per row concatenate to exactly chat_batch()'s text (the
         same U+FFFD holdback as chat_stream)."""
         prompts, budgets, temp, top_p = self._encode_requests(requests)
+        names = self._request_adapters(requests)
         n = len(requests)
         ids = [[] for _ in range(n)]
         sent = [""] * n
         live = [True] * n
         with self._stream_ctx():
             for emitted in self._generate_batch_steps(
-                    prompts, max(budgets), temp, top_p, budgets=budgets):
+                    prompts, max(budgets), temp, top_p, budgets=budgets,
+                    adapters=names):
                 step_rows = set()
                 for i, t in emitted:
                     ids[i].append(t)
@@ -796,12 +916,15 @@ class InferenceEngine:
 
     # ----------------------------------------------------------- score
     @torch.no_grad()
-    def perplexity(self, texts: List[str]) -> float:
+    def perplexity(self, texts: List[str],
+                   adapter: Optional[str] = None) -> float:
+        gi = self._adapter_index(adapter)
         with self._stream_ctx():
-            return self._perplexity(texts)
+            return self._perplexity(texts, gi)
 
-    def _perplexity(self, texts: List[str]) -> float:
+    def _perplexity(self, texts: List[str], gi: int = -1) -> float:
         """Mean perplexity over texts (built-in Scoring metric)."""
+        akw = self._selection([gi])
         losses = []
         for t in texts:
             ids = [self.tok.bos_token_id] + self.tok.encode(t)
@@ -809,7 +932,7 @@ class InferenceEngine:
             if len(ids) < 2:
                 continue
             x = torch.tensor([ids], dtype=torch.long, device=self.device)
-            loss = self.model(x, labels=x)
+            loss = self.model(x, labels=x, **akw)
             losses.append(float(loss))
         if not losses:
             return float("inf")

@@ -63,10 +63,22 @@ class BatchingFront:
         t = threading.Thread(target=self._worker, daemon=True)
         t.start()
 
-    def chat(self, messages, max_tokens, temperature, top_p):
+    @staticmethod
+    def _req(messages, max_tokens, temperature, top_p, adapter):
+        req = {"messages": messages, "max_tokens": max_tokens,
+               "temperature": temperature, "top_p": top_p}
+        if adapter is not None:
+            # multi-adapter serving: the adapter rides in the slot and
+            # is chosen per row of the batch — requests for different
+            # adapters coalesce like any others
+            req["adapter"] = adapter
+        return req
+
+    def chat(self, messages, max_tokens, temperature, top_p,
+             adapter=None):
         ev = threading.Event()
-        slot = {"req": {"messages": messages, "max_tokens": max_tokens,
-                        "temperature": temperature, "top_p": top_p},
+        slot = {"req": self._req(messages, max_tokens, temperature, top_p,
+                                 adapter),
                 "ev": ev}
         self._q.put(slot)
         ev.wait()
@@ -74,13 +86,14 @@ class BatchingFront:
             raise slot["err"]
         return slot["out"]
 
-    def chat_stream(self, messages, max_tokens, temperature, top_p):
+    def chat_stream(self, messages, max_tokens, temperature, top_p,
+                    adapter=None):
         """Streamed request joining the batch: yields text deltas from
         a per-request queue fed by the worker (None = end)."""
         import queue
         tokq = queue.Queue()
-        slot = {"req": {"messages": messages, "max_tokens": max_tokens,
-                        "temperature": temperature, "top_p": top_p},
+        slot = {"req": self._req(messages, max_tokens, temperature, top_p,
+                                 adapter),
                 "tokq": tokq}
         self._q.put(slot)
         while True:
@@ -126,16 +139,18 @@ class BatchingFront:
                 # single-stream (graphed) path instead
                 b = batch[0]
                 r = b["req"]
+                akw = ({"adapter": r["adapter"]} if "adapter" in r
+                       else {})
                 if "tokq" in b:
                     for d in self.engine.chat_stream(
                             r["messages"], r["max_tokens"],
-                            r["temperature"], r["top_p"]):
+                            r["temperature"], r["top_p"], **akw):
                         b["tokq"].put(d)
                     b["tokq"].put(None)
                 else:
                     b["out"] = self.engine.chat(
                         r["messages"], r["max_tokens"],
-                        r["temperature"], r["top_p"])
+                        r["temperature"], r["top_p"], **akw)
                     b["ev"].set()
                 return
             if streaming and hasattr(self.engine,
@@ -174,9 +189,30 @@ class BatchingFront:
                     b["ev"].set()
 
 
-def build_handler(pool, batcher=None, model_name: str = "datatunerx"):
+def build_handler(pool, batcher=None, model_name: str = "datatunerx",
+                  adapter_names=None):
+    """adapter_names: the named adapters of multi-adapter serving. When
+    given, a request's "model" field picks the adapter (absent or equal
+    to model_name: the base model; anything else: 404) and /v1/models
+    lists the base and every adapter. None: the field is ignored."""
     if not isinstance(pool, EnginePool):
         pool = EnginePool([pool])
+    multi = adapter_names is not None
+    adapter_names = tuple(adapter_names or ())
+
+    class _UnknownModel(Exception):
+        pass
+
+    def pick_adapter(body):
+        """kwargs for the engine call from the body's "model"."""
+        if not multi:
+            return {}
+        name = body.get("model") if isinstance(body, dict) else None
+        if name is None or name == model_name:
+            return {}
+        if isinstance(name, str) and name in adapter_names:
+            return {"adapter": name}
+        raise _UnknownModel(name)
 
     class _Lease:
         def __enter__(self):
@@ -206,8 +242,9 @@ def build_handler(pool, batcher=None, model_name: str = "datatunerx"):
             elif self.path in ("/v1/models", "/models"):
                 # OpenAI-SDK discovery call (clients list models first)
                 self._send(200, {"object": "list", "data": [{
-                    "id": model_name, "object": "model",
-                    "owned_by": "datatunerx-amd"}]})
+                    "id": n, "object": "model",
+                    "owned_by": "datatunerx-amd"}
+                    for n in (model_name,) + adapter_names]})
             else:
                 self._send(404, {"error": "not found"})
 
@@ -242,6 +279,7 @@ def build_handler(pool, batcher=None, model_name: str = "datatunerx"):
                                          "temperature/top_p must be "
                                          "numbers"})
                         return
+                    akw = pick_adapter(body)
                     if body.get("stream"):
                         # SSE token streaming (OpenAI chunk format)
                         self.send_response(200)
@@ -260,13 +298,13 @@ def build_handler(pool, batcher=None, model_name: str = "datatunerx"):
                         if batcher is not None:
                             import contextlib
                             lease = contextlib.nullcontext()
-                            gen = batcher.chat_stream(*args)
+                            gen = batcher.chat_stream(*args, **akw)
                         else:
                             lease = None
                         with (lease if lease is not None else lock) \
                                 as engine:
                             if lease is None:
-                                gen = engine.chat_stream(*args)
+                                gen = engine.chat_stream(*args, **akw)
                             for delta in gen:
                                 if client_gone:
                                     continue  # keep consuming to the end
@@ -294,10 +332,10 @@ def build_handler(pool, batcher=None, model_name: str = "datatunerx"):
                     # (non-streaming paths below; a mid-stream failure
                     # must not fall through to _send: headers are gone)
                     if batcher is not None:
-                        text = batcher.chat(*args)
+                        text = batcher.chat(*args, **akw)
                     else:
                         with lock as engine:
-                            text = engine.chat(*args)
+                            text = engine.chat(*args, **akw)
                     self._send(200, {
                         "id": f"chatcmpl-{int(time.time()*1000)}",
                         "object": "chat.completion",
@@ -310,11 +348,15 @@ def build_handler(pool, batcher=None, model_name: str = "datatunerx"):
                         }],
                     })
                 elif self.path in ("/v1/score", "/score"):
+                    akw = pick_adapter(body)
                     with lock as engine:
-                        ppl = engine.perplexity(body.get("texts", []))
+                        ppl = engine.perplexity(body.get("texts", []),
+                                                **akw)
                     self._send(200, {"perplexity": ppl})
                 else:
                     self._send(404, {"error": "not found"})
+            except _UnknownModel as e:
+                self._send(404, {"error": f"unknown model {e.args[0]!r}"})
             except Exception as e:      # surface engine errors as 500s
                 try:
                     self._send(500, {"error": f"{type(e).__name__}: {e}"})
@@ -410,14 +452,72 @@ def parse_args(argv=None):
     ap.add_argument("--port", type=int, default=8000)
     ap.add_argument("--host", default="127.0.0.1")
     ap.add_argument("--model", default="llama2-7b")
-    ap.add_argument("--adapter", default=None)
+    ap.add_argument("--adapter", action="append", default=None,
+                    help="DIR: serve that one adapter (single-adapter "
+                         "mode). NAME=DIR, repeatable: multi-adapter "
+                         "mode — one base model, the adapter chosen per "
+                         "request by its \"model\" field")
     ap.add_argument("--template", default="llama2")
     ap.add_argument("--quantization", choices=("int8", "int4"),
                     default=None,
                     help="serve the base weights weight-only quantized "
                          "(adapters stay bf16, unmerged); single-GPU "
                          "llama models only")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    args.adapter, args.adapters = _split_adapters(ap, args.adapter)
+    return args
+
+
+def _split_adapters(ap, values):
+    """--adapter values -> (single adapter dir | None, {name: dir} |
+    None). One value without '=' is the single-adapter mode; NAME=DIR
+    values select multi-adapter mode; mixing the forms, repeating a
+    plain DIR or repeating a name is a start-up error."""
+    if not values:
+        return None, None
+    named = [v for v in values if "=" in v]
+    if not named:
+        if len(values) > 1:
+            ap.error("--adapter DIR may be given once; use NAME=DIR to "
+                     "serve several adapters")
+        return values[0], None
+    if len(named) != len(values):
+        ap.error("--adapter: do not mix DIR and NAME=DIR forms")
+    out = {}
+    for v in named:
+        name, path = v.split("=", 1)
+        name = name.strip()
+        if not name or not path:
+            ap.error(f"--adapter {v!r}: expected NAME=DIR")
+        if name in out:
+            ap.error(f"--adapter: name {name!r} given twice")
+        out[name] = path
+    return None, out
+
+
+def _check_adapters(args, world: int):
+    """Named adapters are refused at start-up where they cannot be
+    honoured."""
+    if not args.adapters:
+        return
+    if world > 1:
+        raise SystemExit(
+            "named adapters (--adapter NAME=DIR) are not supported with "
+            f"tensor-parallel serving (WORLD_SIZE={world}); serve them on "
+            "one GPU")
+    if args.model in args.adapters:
+        raise SystemExit(
+            f"--adapter: the name {args.model!r} is the base model's")
+    from .engine import builtin_config
+    from ..models.hf_io import is_hf_model_dir
+    if not is_hf_model_dir(args.model):
+        try:
+            family, _ = builtin_config(args.model)
+        except ValueError as e:
+            raise SystemExit(str(e))
+        if family != "llama":
+            raise SystemExit(
+                f"named adapters support llama models, not {args.model!r}")
 
 
 def _check_quantization(args, world: int):
@@ -448,6 +548,7 @@ def main(argv=None):
     args = parse_args(argv)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     _check_quantization(args, world)
+    _check_adapters(args, world)
     if world > 1:
         # tensor-parallel service (launched under torchrun, 1 rank/GPU):
         # rank 0 serves HTTP; followers run the collectives in lockstep.
@@ -503,8 +604,15 @@ def main(argv=None):
     from ..models import LlamaForCausalLM
     from ..models.hf_io import load_tokenizer
     device = torch.device("cuda:0" if torch.cuda.is_available() else "cpu")
-    model = build_model(args.model, device, adapter_dir=args.adapter,
-                        quantization=args.quantization)
+    if args.adapters:
+        try:
+            model = build_model(args.model, device, adapters=args.adapters,
+                                quantization=args.quantization)
+        except (ValueError, OSError) as e:
+            raise SystemExit(f"--adapter: {e}")
+    else:
+        model = build_model(args.model, device, adapter_dir=args.adapter,
+                            quantization=args.quantization)
     tok = load_tokenizer(args.model)
     n_slots = max(1, int(os.environ.get("DTX_SERVE_CONCURRENCY", "2")))
     pool = EnginePool([
@@ -519,8 +627,11 @@ def main(argv=None):
                             device=device, own_stream=True),
             max_batch=int(os.environ.get("DTX_SERVE_MAX_BATCH", "8")))
     httpd = ThreadingHTTPServer((args.host, args.port),
-                                build_handler(pool, batcher,
-                                              model_name=args.model))
+                                build_handler(
+                                    pool, batcher, model_name=args.model,
+                                    adapter_names=(
+                                        list(args.adapters)
+                                        if args.adapters else None)))
     httpd.serve_forever()
 
 
