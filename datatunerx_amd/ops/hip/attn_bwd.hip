@@ -14,7 +14,9 @@
 //     dV[kv][d] += mfma(A=conv(P),  B=dO^T-rows)  (conv = cvt_pk+permlane
 //     dK[kv][d] += mfma(A=conv(dS), B=Q^T-rows)    C-layout -> A-frag)
 // dq kernel (one block = 256 q rows, 8 waves x 32):
-//   wave-resident Q/dO fragments; per kv-tile (64 rows):
+//   wave-resident Q/dO fragments; prologue forms delta = rowsum(dO o O)
+//   from them and writes it for dkdv (launched second); per kv-tile
+//   (64 rows):
 //     S^T, dP^T as in the forward (swapped), then
 //     dQ[q][d] += mfma(A=conv(dS^T), B=K^T-rows)
 //
@@ -23,6 +25,7 @@
 
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
+typedef __attribute__((ext_vector_type(4))) float f32x4;
 
 #define MFMA32(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0)
 #define NEG_INF (-3.0e38f)
@@ -89,48 +92,6 @@ __device__ __forceinline__ void conv_c_to_frag(const f32x16& p,
   f1 = *reinterpret_cast<short8v*>(&hi4);
 }
 
-// ------------------------------------------------------------- delta
-// delta[b,h,s] = sum_d dO[b,s,h,d] * O[b,s,h,d]   (BSHD in, [B,H,S] out)
-// Vectorized: a wave covers 64*8/D rows per iteration with 16B loads
-// (the scalar version ran at ~40% of the HBM roofline).
-template <int D>
-__global__ __launch_bounds__(DTX_BLOCK)
-void attn_delta2_kernel(const unsigned short* __restrict__ dO,
-                        const unsigned short* __restrict__ O,
-                        float* __restrict__ delta,
-                        long nrows, int H, int S) {
-  constexpr int LPR = D / 8;                  // lanes per row
-  constexpr int RPW = 64 / LPR;               // rows per wave
-  const int lane = threadIdx.x & 63;
-  const int wid = threadIdx.x >> 6;
-  const int sub = lane / LPR;                 // row slot in wave
-  const int g = lane % LPR;                   // 16B group in row
-  for (long r0 = ((long)blockIdx.x * 4 + wid) * RPW; r0 < nrows;
-       r0 += (long)gridDim.x * 4 * RPW) {
-    const long row = r0 + sub;
-    float acc = 0.f;
-    if (row < nrows) {
-      const long base = row * D + g * 8;
-      float a[8], b8[8];
-      load_bf16x8(dO + base, a);
-      load_bf16x8(O + base, b8);
-#pragma unroll
-      for (int i = 0; i < 8; ++i) acc += a[i] * b8[i];
-    }
-    // reduce within each LPR-lane group
-#pragma unroll
-    for (int off = LPR / 2; off > 0; off >>= 1)
-      acc += __shfl_xor(acc, off, 64);
-    if (g == 0 && row < nrows) {
-      const int h = (int)(row % H);
-      const long bs = row / H;
-      const int s = (int)(bs % S);
-      const long b = bs / S;
-      delta[((long)b * H + h) * S + s] = acc;
-    }
-  }
-}
-
 // ------------------------------------------------------------- dk/dv
 // 8 waves (512 threads), TWO waves per SIMD: waves 0-3 accumulate dV
 // and waves 4-7 accumulate dK for the same 4x32 kv rows. Splitting the
@@ -167,14 +128,19 @@ void attn_bwd_dkdv2_kernel(const unsigned short* __restrict__ Q,
   __shared__ DkdvLds<D> lds;
   // separate object: float arrays INSIDE DkdvLds made hipcc scalarize
   // every b128 fragment read of the struct (see profiles/README.md)
-  __shared__ float lsed[2][64 + 64];
+  // [slot][0..63] = lse * LOG2E, [slot][64..127] = delta of the stage's
+  // q rows; 16-byte aligned so a tile's rows come back as b128 reads
+  __shared__ __attribute__((aligned(16))) float lsed[2][64 + 64];
 
   const int lane = threadIdx.x & 63;
-  const int wid = threadIdx.x >> 6;
+  // readfirstlane makes wid provably wave-uniform, so kw, role_dv,
+  // live_tile and interior below are scalar branches, not exec masks
+  const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int l31 = lane & 31;
   const int hi = lane >> 5;
   const int rep = Hq / Hkv;
   const bool role_dv = wid < 4;            // waves 0-3 dV, 4-7 dK
+  const short8v zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
 
   const int bh = blockIdx.y;
   const int b = bh / Hkv, hkv = bh % Hkv;
@@ -187,20 +153,27 @@ void attn_bwd_dkdv2_kernel(const unsigned short* __restrict__ Q,
   const float kscale = scale * LOG2E;
 
   // wave-resident K fragments (+ V for the dK waves, which need
-  // dP = dO V^T): lane holds X[kw+l31][kc*16+hi*8+j]
+  // dP = dO V^T): lane holds X[kw+l31][kc*16+hi*8+j].
+  // Every global load in this kernel is UNCONDITIONAL: the row index is
+  // clamped to the last valid row and rows past the end are zeroed by a
+  // select afterwards. A load under a branch cannot be counted by the
+  // compiler's vmcnt bookkeeping, and it then drains the whole stage
+  // prefetch (vmcnt(0)) at the first MFMA of every q-tile. The zeroing
+  // must stay: a clamped row times p = 0 would turn an Inf into NaN.
   short8v kfrag[DC16], vfrag[DC16];
   {
     const int krow = kw + l31;
+    const bool kok = krow < Skv;
+    const long off0 =
+        kbase + (long)min(krow, Skv - 1) * krowstr + hi * 8;
 #pragma unroll
     for (int kc = 0; kc < DC16; ++kc) {
-      kfrag[kc] = short8v{0, 0, 0, 0, 0, 0, 0, 0};
-      vfrag[kc] = short8v{0, 0, 0, 0, 0, 0, 0, 0};
-      if (krow < Skv) {
-        const long off = kbase + (long)krow * krowstr + kc * 16 + hi * 8;
-        kfrag[kc] = *reinterpret_cast<const short8v*>(Kp + off);
-        if (!role_dv)
-          vfrag[kc] = *reinterpret_cast<const short8v*>(Vp + off);
-      }
+      const short8v k8 =
+          *reinterpret_cast<const short8v*>(Kp + off0 + kc * 16);
+      const short8v v8 =
+          *reinterpret_cast<const short8v*>(Vp + off0 + kc * 16);
+      kfrag[kc] = kok ? k8 : zero8;
+      vfrag[kc] = kok ? v8 : zero8;
     }
   }
 
@@ -219,51 +192,48 @@ void attn_bwd_dkdv2_kernel(const unsigned short* __restrict__ Q,
     const int qs_lo = causal ? max(0, (kv0b - diag) / 64) : 0;
     const int qs_hi = (S + 63) / 64;
     // T14 async-stage split: stage qs+1's global loads are issued while
-    // stage qs computes; the LDS write happens after the barrier.
+    // stage qs computes; the LDS write happens after the barrier. The
+    // stage's lse (even waves) / delta (odd waves) ride along in one
+    // VGPR, so they cost no round trip of their own.
     constexpr int RIT = (64 * (D / 8)) / 512;   // row-staging iters
     short8v stg[RIT * 2];
+    float lsv;
     auto issue_stage = [&](int qs) {
+      const int q0s = qs * 64;
 #pragma unroll
       for (int it = 0; it < RIT; ++it) {
         const int idx = threadIdx.x + it * 512;
         const int row = idx / (D / 8), g = idx % (D / 8);
-        const int q0s = qs * 64;
-        short8v q8 = {0, 0, 0, 0, 0, 0, 0, 0};
-        short8v d8 = {0, 0, 0, 0, 0, 0, 0, 0};
-        if (q0s + row < S) {
-          const long off = qbase + (long)(q0s + row) * qrowstr + g * 8;
-          q8 = *reinterpret_cast<const short8v*>(Q + off);
-          d8 = *reinterpret_cast<const short8v*>(dO + off);
-        }
-        stg[it * 2] = q8;
-        stg[it * 2 + 1] = d8;
+        const long off =
+            qbase + (long)min(q0s + row, S - 1) * qrowstr + g * 8;
+        stg[it * 2] = *reinterpret_cast<const short8v*>(Q + off);
+        stg[it * 2 + 1] = *reinterpret_cast<const short8v*>(dO + off);
       }
+      const float* src = (wid & 1) ? delta_in : lse_in;
+      lsv = src[lbase + min(q0s + lane, S - 1)];
     };
-    auto write_stage = [&](int slot) {
+    auto write_stage = [&](int slot, int qs) {
+      const int q0s = qs * 64;
 #pragma unroll
       for (int it = 0; it < RIT; ++it) {
         const int idx = threadIdx.x + it * 512;
         const int row = idx / (D / 8), g = idx % (D / 8);
+        const bool ok = q0s + row < S;
         *reinterpret_cast<short8v*>(&lds.Qr[slot][row][g * 8]) =
-            stg[it * 2];
+            ok ? stg[it * 2] : zero8;
         *reinterpret_cast<short8v*>(&lds.dOr[slot][row][g * 8]) =
-            stg[it * 2 + 1];
+            ok ? stg[it * 2 + 1] : zero8;
       }
-    };
-    auto write_lsed = [&](int slot, int qs) {
-      if (threadIdx.x < 64) {
-        const int qg = qs * 64 + threadIdx.x;
-        lsed[slot][threadIdx.x] = qg < S ? lse_in[lbase + qg] : 0.f;
-        lsed[slot][64 + threadIdx.x] =
-            qg < S ? delta_in[lbase + qg] : 0.f;
+      if (wid < 2) {
+        const float x = q0s + lane < S ? lsv : 0.f;
+        lsed[slot][wid * 64 + lane] = wid ? x : x * LOG2E;
       }
     };
     int cur = 0;
     if (qs_lo < qs_hi) {
       // prologue: first stage lands in slot 0 before the loop
       issue_stage(qs_lo);
-      write_stage(0);
-      write_lsed(0, qs_lo);
+      write_stage(0, qs_lo);
       __syncthreads();
     }
     for (int qs = qs_lo; qs < qs_hi; ++qs) {
@@ -278,6 +248,16 @@ void attn_bwd_dkdv2_kernel(const unsigned short* __restrict__ Q,
       const bool live_tile =
           !(q0 >= S || (causal && (q0 + 31 + diag < kw)));
       if (live_tile) {
+
+      // ---- the tile's lse2 / delta in one shot: the C-layout rows
+      // bw_crow(4g..4g+3, hi) = 8g + 4hi + 0..3 are 4 consecutive
+      // floats, so 4 b128 reads fetch all 16 (dV waves skip delta).
+      // Issued ahead of the MFMAs so their latency sits under them.
+      f32x4 l4[4], d4[4];
+#pragma unroll
+      for (int g = 0; g < 4; ++g)
+        l4[g] = *reinterpret_cast<const f32x4*>(
+            &lsed[cur][qoff + 8 * g + 4 * hi]);
 
       // ---- S[q][kv] (both roles) and dP[q][kv] (dK waves only)
       // C-layout: q rows on regs, kv on lanes = the wave's kw + l31
@@ -304,31 +284,40 @@ void attn_bwd_dkdv2_kernel(const unsigned short* __restrict__ Q,
       }
 
       // ---- P = exp2(s*kscale - lse2); dS = P o (dP - delta) * scale
-      const int kvg = kw + l31;
+      // One uniform choice per tile between the unmasked and the masked
+      // exp loop. P overwrites sv; dS overwrites dpv.
       const bool interior = (kv0b + 128 <= Skv) && (q0 + 32 <= S) &&
                             (!causal || (kw + 31 <= q0 + diag));
-      // P overwrites sv; dS overwrites dpv (keeps the VGPR count spill-free)
+      if (interior) {
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int qg = q0 + bw_crow(r, hi);
-        const float lse2 = lsed[cur][qoff + bw_crow(r, hi)] * LOG2E;
-        const float dlt = lsed[cur][64 + qoff + bw_crow(r, hi)];
-        float p;
-        if (interior) {
-          p = __builtin_exp2f(sv[r] * kscale - lse2);
-        } else {
+        for (int r = 0; r < 16; ++r)
+          sv[r] = __builtin_exp2f(sv[r] * kscale - l4[r >> 2][r & 3]);
+      } else {
+        const int kvg = kw + l31;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int qg = q0 + bw_crow(r, hi);
           const bool dead = (kvg >= Skv) | (qg >= S) |
                             (causal && (kvg > qg + diag));
-          p = dead ? 0.f : __builtin_exp2f(sv[r] * kscale - lse2);
+          sv[r] = dead ? 0.f
+                       : __builtin_exp2f(sv[r] * kscale - l4[r >> 2][r & 3]);
         }
-        sv[r] = p;
-        dpv[r] = p * (dpv[r] - dlt) * scale;
       }
 
       // ---- fragments (k = q) and accumulate this role's output
       short8v f0, f1;
-      if (role_dv) conv_c_to_frag(sv, f0, f1);
-      else conv_c_to_frag(dpv, f0, f1);
+      if (role_dv) {
+        conv_c_to_frag(sv, f0, f1);
+      } else {
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+          d4[g] = *reinterpret_cast<const f32x4*>(
+              &lsed[cur][64 + qoff + 8 * g + 4 * hi]);
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+          dpv[r] = sv[r] * (dpv[r] - d4[r >> 2][r & 3]) * scale;
+        conv_c_to_frag(dpv, f0, f1);
+      }
       const DTX_AS3 unsigned short* img3 = role_dv
           ? (const DTX_AS3 unsigned short*)&lds.dOr[cur][0][0]
           : (const DTX_AS3 unsigned short*)&lds.Qr[cur][0][0];
@@ -344,10 +333,7 @@ void attn_bwd_dkdv2_kernel(const unsigned short* __restrict__ Q,
       }
       }  // live_tile
       }  // qh
-      if (qs + 1 < qs_hi) {
-        write_stage(cur ^ 1);
-        write_lsed(cur ^ 1, qs + 1);
-      }
+      if (qs + 1 < qs_hi) write_stage(cur ^ 1, qs + 1);
       // one barrier per stage: publishes slot cur^1 AND guards the
       // next iteration's write into the slot every wave just read
       __syncthreads();
@@ -385,8 +371,9 @@ void attn_bwd_dq2_kernel(const unsigned short* __restrict__ Q,
                          const unsigned short* __restrict__ Kp,
                          const unsigned short* __restrict__ Vp,
                          const unsigned short* __restrict__ dO,
+                         const unsigned short* __restrict__ O,
                          const float* __restrict__ lse_in,
-                         const float* __restrict__ delta_in,
+                         float* __restrict__ delta_out,
                          unsigned short* __restrict__ dQ,
                          int B, int Hq, int Hkv, int S, int Skv,
                          float scale, int causal) {
@@ -413,20 +400,42 @@ void attn_bwd_dq2_kernel(const unsigned short* __restrict__ Q,
   const int diag = Skv - S;
   const float kscale = scale * LOG2E;
 
-  // wave-resident Q and dO fragments (B-layout: lane q = qw + l31)
+  // wave-resident Q and dO fragments (B-layout: lane q = qw + l31).
+  // delta[q] = sum_d dO[q][d] * O[q][d] is formed here from the dO
+  // fragments the wave holds anyway (no separate pass over dO and O).
+  // The lane holds the 8-element pieces c = 2*kc + hi of its row; they
+  // are summed as a 16B-per-lane row reduction would: each piece in
+  // element order, then an xor butterfly over the piece index (c ^ D/16,
+  // ..., c ^ 2 pair pieces of this lane, c ^ 1 is lane ^ 32). The hi = 0
+  // lane publishes delta for the dkdv kernel, which is launched after
+  // this one on the same stream.
   short8v qfrag[DC16], dofrag[DC16];
   float lse2 = 0.f, dlt = 0.f;
   {
     const int qrow = qw + l31;
     if (qrow < S) {
+      float part[DC16];
 #pragma unroll
       for (int kc = 0; kc < DC16; ++kc) {
         const long off = qbase + (long)qrow * qrowstr + kc * 16 + hi * 8;
         qfrag[kc] = *reinterpret_cast<const short8v*>(Q + off);
         dofrag[kc] = *reinterpret_cast<const short8v*>(dO + off);
+        const short8v o8 = *reinterpret_cast<const short8v*>(O + off);
+        float acc = 0.f;
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+          acc += bf2f((unsigned short)dofrag[kc][j]) *
+                 bf2f((unsigned short)o8[j]);
+        part[kc] = acc;
       }
+#pragma unroll
+      for (int w = DC16 / 2; w > 0; w >>= 1)
+#pragma unroll
+        for (int kc = 0; kc < w; ++kc) part[kc] += part[kc + w];
       lse2 = lse_in[lbase + qrow] * LOG2E;
-      dlt = delta_in[lbase + qrow];
+      // the partner lane has the same qrow, so it is in this branch too
+      dlt = part[0] + __shfl_xor(part[0], 32, 64);
+      if (hi == 0) delta_out[lbase + qrow] = dlt;
     } else {
 #pragma unroll
       for (int kc = 0; kc < DC16; ++kc) {
@@ -566,22 +575,6 @@ void attn_bwd_dq2_kernel(const unsigned short* __restrict__ Q,
 }
 
 // ------------------------------------------------------------- launchers
-void launch_attn_delta(const void* dO, const void* O, float* delta,
-                       long nrows, int H, int S, int D, hipStream_t st) {
-  const int rpw = 64 / (D / 8);
-  long gw = DTX_CDIV(nrows, 4 * rpw);
-  int grid = (int)(gw < 2048 ? (gw < 1 ? 1 : gw) : 2048);
-  if (D == 128) {
-    attn_delta2_kernel<128><<<grid, DTX_BLOCK, 0, st>>>(
-        (const unsigned short*)dO, (const unsigned short*)O, delta,
-        nrows, H, S);
-  } else if (D == 64) {
-    attn_delta2_kernel<64><<<grid, DTX_BLOCK, 0, st>>>(
-        (const unsigned short*)dO, (const unsigned short*)O, delta,
-        nrows, H, S);
-  }
-}
-
 void launch_attn_bwd_dkdv(const void* q, const void* k, const void* v,
                           const void* dO, const float* lse,
                           const float* delta, void* dk, void* dv, int B,
@@ -603,23 +596,24 @@ void launch_attn_bwd_dkdv(const void* q, const void* k, const void* v,
   }
 }
 
+// Also writes delta[B,Hq,S]; launch before launch_attn_bwd_dkdv.
 void launch_attn_bwd_dq(const void* q, const void* k, const void* v,
-                        const void* dO, const float* lse,
-                        const float* delta, void* dq, int B, int Hq,
+                        const void* dO, const void* o, const float* lse,
+                        float* delta, void* dq, int B, int Hq,
                         int Hkv, int S, int Skv, int D, float scale,
                         int causal, hipStream_t st) {
   dim3 grid(DTX_CDIV(S, 256), B * Hq);
   if (D == 128) {
     attn_bwd_dq2_kernel<128><<<grid, 512, 0, st>>>(
         (const unsigned short*)q, (const unsigned short*)k,
-        (const unsigned short*)v,
-        (const unsigned short*)dO, lse, delta, (unsigned short*)dq,
+        (const unsigned short*)v, (const unsigned short*)dO,
+        (const unsigned short*)o, lse, delta, (unsigned short*)dq,
         B, Hq, Hkv, S, Skv, scale, causal);
   } else if (D == 64) {
     attn_bwd_dq2_kernel<64><<<grid, 512, 0, st>>>(
         (const unsigned short*)q, (const unsigned short*)k,
-        (const unsigned short*)v,
-        (const unsigned short*)dO, lse, delta, (unsigned short*)dq,
+        (const unsigned short*)v, (const unsigned short*)dO,
+        (const unsigned short*)o, lse, delta, (unsigned short*)dq,
         B, Hq, Hkv, S, Skv, scale, causal);
   }
 }

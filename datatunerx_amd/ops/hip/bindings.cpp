@@ -64,15 +64,13 @@ void launch_gemm_nt(const void*, const void*, const void*, void*, long,
 void launch_attn_decode(const void*, const void*, const void*,
                         const int*, float*, void*, float*, int, int, int,
                         int, int, float, int, hipStream_t);
-void launch_attn_delta(const void*, const void*, float*, long, int, int,
-                       int, hipStream_t);
 void launch_attn_bwd_dkdv(const void*, const void*, const void*,
                           const void*, const float*, const float*,
                           void*, void*, int, int, int, int, int, int,
                           float, int, hipStream_t);
 void launch_attn_bwd_dq(const void*, const void*, const void*,
-                        const void*, const float*, const float*, void*,
-                        int, int, int, int, int, int, float, int,
+                        const void*, const void*, const float*, float*,
+                        void*, int, int, int, int, int, int, float, int,
                         hipStream_t);
 
 namespace {
@@ -608,24 +606,26 @@ std::vector<torch::Tensor> attn_bwd(torch::Tensor q, torch::Tensor k,
   const int B = (int)q.size(0), S = (int)q.size(1), Hq = (int)q.size(2),
             D = (int)q.size(3);
   const int Skv = (int)k.size(1), Hkv = (int)k.size(2);
+  check_bf16_contig(o, "o");
   auto delta = torch::empty({B, Hq, S}, q.options().dtype(torch::kFloat));
-  launch_attn_delta(dO_c.data_ptr(), o.data_ptr(), delta.data_ptr<float>(),
-                    (long)B * S * Hq, Hq, S, D, cur_stream());
   // dkdv and dq gather their B-fragments from the ROW-major LDS tiles
   // with ds_read_b64_tr_b16 (tr_bfrag) — no pre-transposed Q/K/dO
   // copies, no transpose_sd pre-passes in the backward at all
   auto dq = torch::empty_like(q);
   auto dk = torch::empty_like(k);
   auto dv = torch::empty_like(v);
+  // dq goes first: its prologue forms delta = rowsum(dO o O) from the dO
+  // fragments it holds and writes it; dkdv, next on the same stream,
+  // reads it. There is no separate delta pass.
+  launch_attn_bwd_dq(q.data_ptr(), k.data_ptr(), v.data_ptr(),
+                     dO_c.data_ptr(), o.data_ptr(), lse.data_ptr<float>(),
+                     delta.data_ptr<float>(), dq.data_ptr(), B, Hq, Hkv, S,
+                     Skv, D, (float)scale, causal ? 1 : 0, cur_stream());
   launch_attn_bwd_dkdv(q.data_ptr(), k.data_ptr(), v.data_ptr(),
                        dO_c.data_ptr(), lse.data_ptr<float>(),
                        delta.data_ptr<float>(), dk.data_ptr(),
                        dv.data_ptr(), B, Hq, Hkv, S, Skv, D,
                        (float)scale, causal ? 1 : 0, cur_stream());
-  launch_attn_bwd_dq(q.data_ptr(), k.data_ptr(), v.data_ptr(),
-                     dO_c.data_ptr(), lse.data_ptr<float>(),
-                     delta.data_ptr<float>(), dq.data_ptr(), B, Hq, Hkv, S,
-                     Skv, D, (float)scale, causal ? 1 : 0, cur_stream());
   return {dq, dk, dv};
 }
 

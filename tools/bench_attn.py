@@ -3,7 +3,14 @@
 
 Reports ms + effective TF/s per kernel (causal ~halves the useful
 flops; we count the causal flops actually computed: full tiles below
-the diagonal + masked diagonal tiles)."""
+the diagonal + masked diagonal tiles).
+
+  python tools/bench_attn.py --batch 64        # the bench.py shape
+
+For per-kernel times run it under the profiler, in a run of its own:
+  rocprofv3 --kernel-trace --stats -d OUT -- python tools/bench_attn.py --batch 64
+"""
+import argparse
 import os
 import sys
 import time
@@ -16,7 +23,11 @@ from datatunerx_amd.ops import _dtx_hip
 
 assert torch.cuda.is_available()
 dev = torch.device("cuda:0")
-B, H, S, D = 16, 32, 1024, 128
+ap = argparse.ArgumentParser()
+ap.add_argument("--batch", type=int, default=16,
+                help="batch size (bench.py's Llama-2-7B shape is 64)")
+args = ap.parse_args()
+B, H, S, D = args.batch, 32, 1024, 128
 scale = D ** -0.5
 
 q = torch.randn(B, S, H, D, device=dev, dtype=torch.bfloat16)
@@ -38,7 +49,7 @@ def bench(fn, iters=20):
 
 # causal: ~1/2 the S^2 work
 fwd_fl = 4 * B * H * S * S * D * 0.5
-bwd_dkdv_fl = fwd_fl / 2 * 5          # S,dP,dV,dK + exp overhead ~ 2.5x fwd
+bwd_dkdv_fl = fwd_fl / 2 * 4          # useful matmuls: S, dP, dV, dK
 bwd_dq_fl = fwd_fl / 2 * 3
 
 t = bench(lambda: ops.attn_fwd(q, k, v, True, scale))
