@@ -2,9 +2,10 @@
 //
 // v2 — 8-wave 32x32-MFMA structure matching attn_fwd.hip, BSHD layout.
 // Recompute strategy: P = exp2(S*scale*log2e - lse*log2e) from the saved
-// lse (no S x S materialization). Host pre-transposes Q, K, dO once per
-// call with transpose_sd ([B,S,H,D] -> [B,H,D,S]) so every LDS staging
-// load is a coalesced 16-byte row read.
+// lse (no S x S materialization). Q, K, V and dO are read in place as
+// BSHD rows (coalesced 16-byte loads); the transposed operands the dV/dK/dQ
+// MFMAs need come from hardware transpose reads of the row-major LDS
+// tiles (tr_bfrag, dtx_mfma.h) — no host-side transposes.
 //
 // dkdv kernel (one block = 256 kv rows, 8 waves x 32):
 //   wave-resident K fragments; V re-read from LDS; per q-tile (32 rows):
@@ -21,76 +22,7 @@
 //     dQ[q][d] += mfma(A=conv(dS^T), B=K^T-rows)
 //
 // Numerics contract: ops/reference.py attn_bwd.
-#include "dtx_common.h"
-
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-
-#define MFMA32(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0)
-#define NEG_INF (-3.0e38f)
-#define LOG2E 1.4426950408889634f
-
-__device__ __forceinline__ unsigned bw_cvt_pk_bf16(float lo, float hi) {
-  unsigned r;
-  asm volatile("v_cvt_pk_bf16_f32 %0, %1, %2\n\ts_nop 1"
-               : "=v"(r) : "v"(lo), "v"(hi));
-  return r;
-}
-
-__device__ __forceinline__ int bw_crow(int r, int hi) {
-  return (r & 3) + 8 * (r >> 2) + 4 * hi;
-}
-
-// MFMA B-fragment gathered from a ROW-major [k][n] LDS image with
-// ds_read_b64_tr_b16 (gfx950 hardware 4x4 transpose read) — replaces
-// the separately-staged transposed image. Verified mapping
-// (tools/probe_tr.cpp): with 16-lane-group addresses
-// R_i = &img[k0 + (i>>2)][n0 + 4*(i&3)], lane l = 4a+c receives
-// component j = img[k0 + j][n0 + (l&15)] — exactly B[k][n=l&31] when
-// n0 = 32-col base + 16*((l>>4)&1). Two reads cover the lane's 8 ks.
-typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
-#define DTX_AS3 __attribute__((address_space(3)))
-// img must be an address_space(3) pointer so all address math stays in
-// 32-bit LDS offsets (a generic pointer here costs 64-bit address
-// arithmetic per read and ~+120 VGPRs in the dkdv kernel).
-template <int STRIDE>
-__device__ __forceinline__ short8v tr_bfrag(
-    const DTX_AS3 unsigned short* img, int k0, int n0, int lane) {
-  const int row = k0 + ((lane >> 2) & 3);
-  const int col = n0 + ((lane >> 4) & 1) * 16 + (lane & 3) * 4;
-  const DTX_AS3 unsigned short* p = img + row * STRIDE + col;
-  union { bf16x4 v[2]; short8v s; } u;
-  u.v[0] = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-      (DTX_AS3 bf16x4*)p);
-  u.v[1] = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-      (DTX_AS3 bf16x4*)(p + 4 * STRIDE));
-  return u.s;
-}
-
-// C-layout f32x16 (rows R on regs, cols on lanes) -> two bf16 A/B
-// fragments with k = R (frag0: R 0..15, frag1: R 16..31).
-__device__ __forceinline__ void conv_c_to_frag(const f32x16& p,
-                                               short8v& f0, short8v& f1) {
-  unsigned c0 = bw_cvt_pk_bf16(p[0], p[1]);
-  unsigned c1 = bw_cvt_pk_bf16(p[2], p[3]);
-  unsigned c2 = bw_cvt_pk_bf16(p[4], p[5]);
-  unsigned c3 = bw_cvt_pk_bf16(p[6], p[7]);
-  unsigned c4 = bw_cvt_pk_bf16(p[8], p[9]);
-  unsigned c5 = bw_cvt_pk_bf16(p[10], p[11]);
-  unsigned c6 = bw_cvt_pk_bf16(p[12], p[13]);
-  unsigned c7 = bw_cvt_pk_bf16(p[14], p[15]);
-  auto r02 = __builtin_amdgcn_permlane32_swap(c0, c2, false, false);
-  auto r13 = __builtin_amdgcn_permlane32_swap(c1, c3, false, false);
-  auto r46 = __builtin_amdgcn_permlane32_swap(c4, c6, false, false);
-  auto r57 = __builtin_amdgcn_permlane32_swap(c5, c7, false, false);
-  u32x4 lo{(unsigned)r02[0], (unsigned)r13[0],
-           (unsigned)r02[1], (unsigned)r13[1]};
-  u32x4 hi4{(unsigned)r46[0], (unsigned)r57[0],
-            (unsigned)r46[1], (unsigned)r57[1]};
-  f0 = *reinterpret_cast<short8v*>(&lo);
-  f1 = *reinterpret_cast<short8v*>(&hi4);
-}
+#include "dtx_mfma.h"
 
 // ------------------------------------------------------------- dk/dv
 // 8 waves (512 threads), TWO waves per SIMD: waves 0-3 accumulate dV
@@ -250,7 +182,7 @@ void attn_bwd_dkdv2_kernel(const unsigned short* __restrict__ Q,
       if (live_tile) {
 
       // ---- the tile's lse2 / delta in one shot: the C-layout rows
-      // bw_crow(4g..4g+3, hi) = 8g + 4hi + 0..3 are 4 consecutive
+      // crow(4g..4g+3, hi) = 8g + 4hi + 0..3 are 4 consecutive
       // floats, so 4 b128 reads fetch all 16 (dV waves skip delta).
       // Issued ahead of the MFMAs so their latency sits under them.
       f32x4 l4[4], d4[4];
@@ -296,7 +228,7 @@ void attn_bwd_dkdv2_kernel(const unsigned short* __restrict__ Q,
         const int kvg = kw + l31;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int qg = q0 + bw_crow(r, hi);
+          const int qg = q0 + crow(r, hi);
           const bool dead = (kvg >= Skv) | (qg >= S) |
                             (causal && (kvg > qg + diag));
           sv[r] = dead ? 0.f
@@ -345,7 +277,7 @@ void attn_bwd_dkdv2_kernel(const unsigned short* __restrict__ Q,
   unsigned short* out = role_dv ? dV : dK;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const int kvg = kw + bw_crow(r, hi);
+    const int kvg = kw + crow(r, hi);
     if (kvg < Skv) {
       unsigned short* orow = out + kbase + (long)kvg * krowstr;
 #pragma unroll
@@ -526,7 +458,7 @@ void attn_bwd_dq2_kernel(const unsigned short* __restrict__ Q,
           if (interior) {
             p = __builtin_exp2f(st[r] * kscale - lse2);
           } else {
-            const int kvg = kv0 + ss * 32 + bw_crow(r, hi);
+            const int kvg = kv0 + ss * 32 + crow(r, hi);
             const bool dead = (kvg >= Skv) | (qg >= S) |
                               (causal && (kvg > qg + diag));
             p = dead ? 0.f : __builtin_exp2f(st[r] * kscale - lse2);
@@ -564,7 +496,7 @@ void attn_bwd_dq2_kernel(const unsigned short* __restrict__ Q,
   // ---- epilogue: dQ C-layout [q regs][d lanes] -> BSHD stores
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const int qg = qw + bw_crow(r, hi);
+    const int qg = qw + crow(r, hi);
     if (qg < S) {
       unsigned short* qrow = dQ + qbase + (long)qg * qrowstr;
 #pragma unroll

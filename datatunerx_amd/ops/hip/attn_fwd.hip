@@ -4,68 +4,27 @@
 // ladder"): block = 512 threads = 8 waves, each wave owns 32 q-rows
 // (QBLK=32, block covers 256), KV tiles of 64 staged in LDS.
 //
-//  - Layout is BSHD (q/k: [B,S,H,D]) — no transpose copies in the model;
-//    V arrives PRE-TRANSPOSED as VT [B,Hkv,D,Skv] (transpose_sd kernel).
+//  - Layout is BSHD (q/k/v: [B,S,H,D]) — no transpose copies anywhere:
+//    V stays row-major and its PV B-fragments come from hardware
+//    transpose reads (tr_bfrag, dtx_mfma.h).
 //  - Swapped QK^T: S^T[kv][q] = mfma(A=K-frag, B=Q-frag) puts a whole
 //    P-row (over kv) in each lane's registers -> softmax (row max, exp2,
 //    row sum) is lane-local; the cross-half reduce is one shfl_xor(32).
 //  - P(C-layout) -> PV A-fragments via v_cvt_pk_bf16_f32 +
 //    permlane32_swap (16 cvt + 8 swaps per tile, no LDS round trip).
-//  - PV unswapped: O[q][d] = mfma(A=P, B=V^T-frag from the VT tile); the
-//    per-q-row rescale factor is fetched with one ds_bpermute per
-//    accumulator row.
-//  - K LDS tile [64][D+8] and VT tile [D][64+8]: +8 padding makes the
-//    column-subtile ds_read_b128 fragment reads bank-conflict-free
-//    (row strides 68/36 dwords; distinct (4r mod 64) starts per group).
+//  - PV unswapped: O[q][d] = mfma(A=P, B=V-frag tr-read from the
+//    row-major V tile); the per-q-row rescale factor is fetched with one
+//    ds_bpermute per accumulator row.
+//  - K and V LDS tiles are both [128][D+8], double-buffered: +8 padding
+//    makes the column-subtile ds_read_b128 K-fragment reads
+//    bank-conflict-free (row stride 68/36 dwords; distinct (4r mod 64)
+//    starts per group).
 //
 // Numerics contract: ops/reference.py attn_fwd (fp32 softmax, exp2
 // domain internally, natural-log lse out). Causal + GQA + ragged S by
 // masking; interior tiles skip the mask; waves fully above the causal
 // diagonal skip compute.
-#include "dtx_common.h"
-
-
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned int uint2_t;
-
-#define MFMA32(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0)
-#define NEG_INF (-3.0e38f)
-#define LOG2E 1.4426950408889634f
-#define LN2 0.6931471805599453f
-
-__device__ __forceinline__ unsigned cvt_pk_bf16(float lo, float hi) {
-  unsigned r;
-  // s_nop 1 covers the VALU-write -> v_permlane read hazard window
-  // (guide T21) for the swap that consumes this value next.
-  asm volatile("v_cvt_pk_bf16_f32 %0, %1, %2\n\ts_nop 1"
-               : "=v"(r) : "v"(lo), "v"(hi));
-  return r;
-}
-
-// C-layout row index for f32x16 accumulator register r (32x32 MFMA).
-__device__ __forceinline__ int crow(int r, int hi) {
-  return (r & 3) + 8 * (r >> 2) + 4 * hi;
-}
-
-// MFMA B-fragment from a ROW-major [k][n] LDS image via the gfx950
-// hardware transpose read (mapping verified by tools/probe_tr.cpp;
-// see attn_bwd.hip tr_bfrag for the derivation).
-typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4f;
-#define DTX_AS3F __attribute__((address_space(3)))
-template <int STRIDE>
-__device__ __forceinline__ short8v fw_tr_bfrag(
-    const DTX_AS3F unsigned short* img, int k0, int n0, int lane) {
-  const int row = k0 + ((lane >> 2) & 3);
-  const int col = n0 + ((lane >> 4) & 1) * 16 + (lane & 3) * 4;
-  const DTX_AS3F unsigned short* p = img + row * STRIDE + col;
-  union { bf16x4f v[2]; short8v s; } u;
-  u.v[0] = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-      (DTX_AS3F bf16x4f*)p);
-  u.v[1] = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-      (DTX_AS3F bf16x4f*)(p + 4 * STRIDE));
-  return u.s;
-}
+#include "dtx_mfma.h"
 
 template <int D>
 struct AttnFwdLds {
@@ -75,13 +34,10 @@ struct AttnFwdLds {
   unsigned short V[2][128][D + 8];  // row-major; PV B-frags via tr-read
 };
 
-// WAVES: q-rows per workgroup = 32*WAVES. 8 (256 rows) shares each
-// staged K/V tile across more q-rows; 4 (128 rows) halves the causal
-// wave-skew inside the workgroup (utilization 82.5% -> 91.7% at
-// S=1024) and lets TWO workgroups co-reside per CU. Measured A/B picks
-// the launcher default.
-template <int D, int WAVES = 8>
-__global__ __launch_bounds__(64 * WAVES, 1)
+// 8 waves x 32 q-rows per workgroup. A 4-wave (128-row) workgroup measured
+// 45% slower on the training shape: profiles/README.md, "Attention round 2".
+template <int D>
+__global__ __launch_bounds__(512, 1)
 void attn_fwd2_kernel(const unsigned short* __restrict__ Q,
                       const unsigned short* __restrict__ Kp,
                       const unsigned short* __restrict__ Vp,
@@ -102,8 +58,8 @@ void attn_fwd2_kernel(const unsigned short* __restrict__ Q,
   const int bh = blockIdx.y;
   const int b = bh / Hq, hq = bh % Hq;
   const int hkv = hq / (Hq / Hkv);
-  constexpr int TPB = 64 * WAVES;
-  constexpr int QROWS = 32 * WAVES;
+  constexpr int TPB = 512;
+  constexpr int QROWS = 256;
   const int q0 = blockIdx.x * QROWS;
   const int qw = q0 + wid * 32;            // wave's first q row
 
@@ -262,27 +218,8 @@ void attn_fwd2_kernel(const unsigned short* __restrict__ Q,
       // ---- P (C-layout f32) -> bf16 A-fragments [q][kv-slice]
       short8v pa[4];
 #pragma unroll
-      for (int ss = 0; ss < 2; ++ss) {
-        const f32x16& p = ss ? s1v : s0v;
-        unsigned c0 = cvt_pk_bf16(p[0], p[1]);
-        unsigned c1 = cvt_pk_bf16(p[2], p[3]);
-        unsigned c2 = cvt_pk_bf16(p[4], p[5]);
-        unsigned c3 = cvt_pk_bf16(p[6], p[7]);
-        unsigned c4 = cvt_pk_bf16(p[8], p[9]);
-        unsigned c5 = cvt_pk_bf16(p[10], p[11]);
-        unsigned c6 = cvt_pk_bf16(p[12], p[13]);
-        unsigned c7 = cvt_pk_bf16(p[14], p[15]);
-        auto r02 = __builtin_amdgcn_permlane32_swap(c0, c2, false, false);
-        auto r13 = __builtin_amdgcn_permlane32_swap(c1, c3, false, false);
-        auto r46 = __builtin_amdgcn_permlane32_swap(c4, c6, false, false);
-        auto r57 = __builtin_amdgcn_permlane32_swap(c5, c7, false, false);
-        u32x4 lo{(unsigned)r02[0], (unsigned)r13[0],
-                 (unsigned)r02[1], (unsigned)r13[1]};
-        u32x4 hi4{(unsigned)r46[0], (unsigned)r57[0],
-                  (unsigned)r46[1], (unsigned)r57[1]};
-        pa[2 * ss + 0] = *reinterpret_cast<short8v*>(&lo);
-        pa[2 * ss + 1] = *reinterpret_cast<short8v*>(&hi4);
-      }
+      for (int ss = 0; ss < 2; ++ss)
+        conv_c_to_frag(ss ? s1v : s0v, pa[2 * ss], pa[2 * ss + 1]);
 
       // ---- rescale O rows by alpha[q-row] (one bpermute per row)
       if (!defer && (st2 > 0 || half > 0)) {
@@ -298,13 +235,13 @@ void attn_fwd2_kernel(const unsigned short* __restrict__ Q,
       // ks OUTER so consecutive MFMAs hit DIFFERENT accumulators
       // (o_acc[0..3]) — back-to-back MFMAs on one accumulator pay the
       // full RAW latency (guide: SQ_WAIT_INST_ANY).
-      const DTX_AS3F unsigned short* v3 =
-          (const DTX_AS3F unsigned short*)&lds.V[cur][0][0];
+      const DTX_AS3 unsigned short* v3 =
+          (const DTX_AS3 unsigned short*)&lds.V[cur][0][0];
 #pragma unroll
       for (int ks = 0; ks < 4; ++ks) {
 #pragma unroll
         for (int c = 0; c < ND32; ++c) {
-          short8v vf = fw_tr_bfrag<D + 8>(v3, koff + ks * 16 + hi * 8,
+          short8v vf = tr_bfrag<D + 8>(v3, koff + ks * 16 + hi * 8,
                                           c * 32, lane);
           o_acc[c] = MFMA32(pa[ks], vf, o_acc[c]);
         }
@@ -347,8 +284,10 @@ void attn_fwd2_kernel(const unsigned short* __restrict__ Q,
   }
 }
 
-// ---------------------------------------------------------------- V^T
+// ---------------------------------------------------------- transpose
 // [B,S,H,D] -> [B,H,D,S] tile transpose (64x64 tiles through LDS).
+// No op calls it any more (attention reads row-major tiles with
+// tr-reads); it stays as an exported, tested utility.
 __global__ __launch_bounds__(256)
 void transpose_sd_kernel(const unsigned short* __restrict__ X,
                          unsigned short* __restrict__ XT,
@@ -399,40 +338,27 @@ void launch_transpose_sd(const void* x, void* xt, int B, int S, int H,
       (const unsigned short*)x, (unsigned short*)xt, B, S, H, D);
 }
 
+template <int D>
+static void launch_attn_fwd_d(const void* q, const void* k, const void* v,
+                              void* o, float* lse, int B, int Hq, int Hkv,
+                              int S, int Skv, float scale, int causal,
+                              hipStream_t st) {
+  dim3 grid(DTX_CDIV(S, 256), B * Hq);
+  attn_fwd2_kernel<D><<<grid, 512, 0, st>>>(
+      (const unsigned short*)q, (const unsigned short*)k,
+      (const unsigned short*)v, (unsigned short*)o, lse,
+      B, Hq, Hkv, S, Skv, scale, causal);
+}
+
 void launch_attn_fwd(const void* q, const void* k, const void* v, void* o,
                      float* lse, int B, int Hq, int Hkv, int S, int Skv,
                      int D, float scale, int causal, hipStream_t st) {
-  // 4-wave workgroups measured 45% SLOWER than 8-wave on the training
-  // shape (a second 256-thread WG does not co-reside at 256 VGPRs, so
-  // half the CU idles); keep 8-wave and leave the variant for probes.
-  const bool w4 = getenv("DTX_ATTN_W4") != nullptr;
-  if (w4) {
-    dim3 grid(DTX_CDIV(S, 128), B * Hq);
-    if (D == 128) {
-      attn_fwd2_kernel<128, 4><<<grid, 256, 0, st>>>(
-          (const unsigned short*)q, (const unsigned short*)k,
-          (const unsigned short*)v, (unsigned short*)o, lse,
-          B, Hq, Hkv, S, Skv, scale, causal);
-    } else if (D == 64) {
-      attn_fwd2_kernel<64, 4><<<grid, 256, 0, st>>>(
-          (const unsigned short*)q, (const unsigned short*)k,
-          (const unsigned short*)v, (unsigned short*)o, lse,
-          B, Hq, Hkv, S, Skv, scale, causal);
-    }
-    return;
-  }
-  dim3 grid(DTX_CDIV(S, 256), B * Hq);
-  if (D == 128) {
-    attn_fwd2_kernel<128, 8><<<grid, 512, 0, st>>>(
-        (const unsigned short*)q, (const unsigned short*)k,
-        (const unsigned short*)v, (unsigned short*)o, lse,
-        B, Hq, Hkv, S, Skv, scale, causal);
-  } else if (D == 64) {
-    attn_fwd2_kernel<64, 8><<<grid, 512, 0, st>>>(
-        (const unsigned short*)q, (const unsigned short*)k,
-        (const unsigned short*)v, (unsigned short*)o, lse,
-        B, Hq, Hkv, S, Skv, scale, causal);
-  }
+  if (D == 128)
+    launch_attn_fwd_d<128>(q, k, v, o, lse, B, Hq, Hkv, S, Skv, scale,
+                           causal, st);
+  else if (D == 64)
+    launch_attn_fwd_d<64>(q, k, v, o, lse, B, Hq, Hkv, S, Skv, scale,
+                          causal, st);
 }
 
 // ------------------------------------------------------- decode (S=1)

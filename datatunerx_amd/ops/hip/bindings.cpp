@@ -330,7 +330,7 @@ torch::Tensor transpose_sd(torch::Tensor x) {
   return xt;
 }
 
-// q,k: [B,S,H,D] BSHD; vt: [B,Hkv,D,Skv] (pre-transposed V).
+// q: [B,S,Hq,D]; k, v: [B,Skv,Hkv,D] — all BSHD, v row-major like k.
 std::vector<torch::Tensor> attn_fwd(torch::Tensor q, torch::Tensor k,
                                     torch::Tensor v, bool causal,
                                     double scale) {
@@ -594,7 +594,7 @@ std::vector<torch::Tensor> attn_decode(torch::Tensor q, torch::Tensor k,
   return {o, lse};
 }
 
-// All BSHD; v untransposed. Pre-transposes Q/K/dO internally.
+// All BSHD, read in place: nothing is transposed on the host side.
 std::vector<torch::Tensor> attn_bwd(torch::Tensor q, torch::Tensor k,
                                     torch::Tensor v, torch::Tensor o,
                                     torch::Tensor dO, torch::Tensor lse,

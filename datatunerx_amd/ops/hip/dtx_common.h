@@ -48,7 +48,10 @@ __device__ __forceinline__ void store_bf16x8(unsigned short* p,
 }
 
 // round two floats to bf16 (RNE) with one v_cvt_pk_bf16_f32 — ~3x
-// cheaper than the scalar f2bf path (no branch, no integer rounding)
+// cheaper than the scalar f2bf path (no branch, no integer rounding).
+// The trailing s_nop 1 covers the VALU-write -> v_permlane read hazard
+// window (guide T21) for callers that feed the result straight into a
+// permlane32_swap (conv_c_to_frag in dtx_mfma.h).
 __device__ __forceinline__ unsigned dtx_cvt_pk_bf16(float lo, float hi) {
   unsigned r;
   asm volatile("v_cvt_pk_bf16_f32 %0, %1, %2\n\ts_nop 1"

@@ -12,11 +12,7 @@
 // All skinny/memory-bound: the roofline is streaming X/Y at HBM rate.
 // R is a compile-time bound so accumulators stay in VGPRs (guide §5.4
 // rule 20).
-#include "dtx_common.h"
-
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-
-#define MFMA32L(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0)
+#include "dtx_mfma.h"
 
 // ---------------------------------------------------------------- contract
 // One wave = one 32-row m-tile x 32-col r-tile (cols >= r zero-padded).
@@ -96,13 +92,13 @@ void lora_contract_kernel(const unsigned short* __restrict__ X,
           }
           short8v wf = *reinterpret_cast<const short8v*>(
               &wlds[l31][kc + hi * 8]);
-          acc = MFMA32L(xf, wf, acc);
+          acc = MFMA32(xf, wf, acc);
         }
         // C-layout: col = r-index = rt + l31, row m = crow(q,hi)
         if (rt + l31 < r) {
 #pragma unroll
           for (int q = 0; q < 16; ++q) {
-            const long m = mw + (q & 3) + 8 * (q >> 2) + 4 * hi;
+            const long m = mw + crow(q, hi);
             if (m < M) {
               if (kc0 == k0)
                 pout[m * r + rt + l31] = acc[q];

@@ -37,11 +37,9 @@
 // Tails: rows past N-1 alias onto a valid row for loads and are never
 // stored; lanes past K load nothing and feed zeros in BOTH operands;
 // batch rows >= M are zeros in registers. Row offsets are long.
-#include "dtx_common.h"
+#include "dtx_mfma.h"
 
 typedef __attribute__((ext_vector_type(4))) unsigned uint4q;
-
-#define QG_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0)
 
 typedef __attribute__((ext_vector_type(2))) float qg_f32x2;
 typedef __attribute__((ext_vector_type(2))) __bf16 qg_bf16x2;
@@ -240,7 +238,7 @@ void qgemm_mfma_kernel(const unsigned short* __restrict__ X,
             a.u[2 * d] = qg_pack_bf16(qg_sbyte(u, 0), qg_sbyte(u, 1));
             a.u[2 * d + 1] = qg_pack_bf16(qg_sbyte(u, 2), qg_sbyte(u, 3));
           }
-          acc[t] = QG_MFMA(a.v, xf[j], acc[t]);
+          acc[t] = MFMA16(a.v, xf[j], acc[t]);
         }
       }
     } else {
@@ -277,7 +275,7 @@ void qgemm_mfma_kernel(const unsigned short* __restrict__ X,
         sxu[u] = (float4v){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int j = 0; j < 4; ++j)
-          sxu[u] = QG_MFMA(ones.v, xm[u][j], sxu[u]);
+          sxu[u] = MFMA16(ones.v, xm[u][j], sxu[u]);
       }
 #pragma unroll
       for (int t = 0; t < T; ++t) {
@@ -293,7 +291,7 @@ void qgemm_mfma_kernel(const unsigned short* __restrict__ X,
             a.u[i] = ((wv[t][j] >> (4 * i)) & 0x000F000Fu) | 0x43004300u;
 #pragma unroll
           for (int u = 0; u < GPS; ++u)
-            part[u] = QG_MFMA(a.v, xm[u][j], part[u]);
+            part[u] = MFMA16(a.v, xm[u][j], part[u]);
         }
 #pragma unroll
         for (int u = 0; u < GPS; ++u) {

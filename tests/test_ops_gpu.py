@@ -357,6 +357,9 @@ def test_gemv(N, K):
     (2048, 11008, 4096),      # gate/up shape family
     (1024, 4096, 11008),      # down-proj (big K)
     (384, 1280, 192),         # odd-but-supported dims
+    (2048, 1024, 128),        # smallest cluster-grid shape (8 x 4 blocks)
+    (2100, 512, 128),         # snake grid: 9 row blocks = group of 8 +
+                              # partial group of 1, with an M tail
 ])
 def test_gemm_nt(M, N, K):
     a, b = mk(M, K), mk(N, K)
@@ -365,8 +368,11 @@ def test_gemm_nt(M, N, K):
     assert_close(c, want, name=f"gemm_nt {M}x{N}x{K}")
 
 
-def test_gemm_nt_src_fused():
-    M, N, K = 777, 1024, 512
+@pytest.mark.parametrize("M,N,K", [
+    (777, 1024, 512),         # snake grid, M tail
+    (2048, 1024, 128),        # cluster grid
+])
+def test_gemm_nt_src_fused(M, N, K):
     a, b, src = mk(M, K), mk(N, K), mk(M, N)
     c = ops.gemm_nt(a, b, src)
     want = a.float() @ b.float().t() + src.float()
