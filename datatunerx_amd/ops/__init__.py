@@ -226,6 +226,43 @@ def lora_wgrad(t, x, scale: float = 1.0, mask=None, seed: int = 0,
     return ref.lora_wgrad(t, x, scale, mask, seed, keep)
 
 
+# Dual forms: two adapters that share one activation (the q and v LoRA
+# pairs of an attention input) in ONE pass over it. Seed-mode dropout
+# only, one seed per adapter. Adapters come in the layout the kernels
+# read: w0/w1 and a0/a1 are [r,K] / [r,N] (native lora_A; lora_B
+# transposed once by the caller).
+def lora_contract2(x, w0, w1, seed0: int = 0, seed1: int = 0,
+                   keep: float = 1.0):
+    """(t0, t1), each bit-identical to lora_contract(x, w, None, seed,
+    keep) with its own adapter and seed."""
+    if _gpu(x):
+        if w0.shape[0] <= 16:
+            return tuple(_EXT.lora_contract2(x, w0, w1, seed0, seed1, keep))
+        return (_EXT.lora_contract(x, w0, None, seed0, keep),
+                _EXT.lora_contract(x, w1, None, seed1, keep))
+    return ref.lora_contract2(x, w0, w1, seed0, seed1, keep)
+
+
+def lora_expand_add_t(y, t, wt, scale: float, mask=None, seed: int = 0,
+                      keep: float = 1.0):
+    """lora_expand_add with the adapter already in [r,N]."""
+    if _gpu(y):
+        _EXT.lora_expand_add_t(y, t, wt, scale, mask, seed, keep)
+        return y
+    return ref.lora_expand_add_t(y, t, wt, scale, mask, seed, keep)
+
+
+def lora_expand_add2(y, t0, t1, a0, a1, scale: float, seed0: int = 0,
+                     seed1: int = 0, keep: float = 1.0):
+    """In place: y += mask0 o (s * t0 @ a0) + mask1 o (s * t1 @ a1), one
+    read-modify-write and one rounding of y (r <= 16, N % 8 == 0)."""
+    if _gpu(y):
+        _EXT.lora_expand_add2(y, t0, t1, a0, a1, scale, seed0, seed1, keep)
+        return y
+    return ref.lora_expand_add2(y, t0, t1, a0, a1, scale, seed0, seed1,
+                                keep)
+
+
 def dropout_mask(M: int, K: int, seed: int, keep: float, like):
     """Materialize the RNG mask (bit-identical to the fused kernels'
     in-kernel bits) — tests and the r>16 fallback path."""

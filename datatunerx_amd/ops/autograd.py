@@ -10,7 +10,8 @@ import os
 
 import torch
 
-from . import (attn_bwd, attn_fwd, lora_contract, lora_expand_add,
+from . import (attn_bwd, attn_fwd, lora_contract, lora_contract2,
+               lora_expand_add, lora_expand_add2, lora_expand_add_t,
                lora_wgrad, rmsnorm_bwd, rmsnorm_fwd, rope_bwd, rope_fwd,
                softmax_xent_bwd, softmax_xent_fwd, swiglu_bwd, swiglu_fwd)
 
@@ -373,7 +374,15 @@ class QKVProj(torch.autograd.Function):
     backward accumulates all three dgrads (and the LoRA dx terms, which
     were already in-place) into ONE dx buffer via addmm_ — removing the
     two [M,E] grad-adds autograd inserts per decoder layer for the
-    shared attention input."""
+    shared attention input.
+
+    The q and v adapters share x: one dual contract in the forward (two
+    dropout seeds, one read of x) and one dual expand-add in the
+    backward (one read-modify-write and one rounding of dx). The two
+    lora_A gradients stay two wgrad calls — a one-pass dual wgrad
+    measured slower (profiles/README.md). lora_B is transposed once in
+    the forward and the copy reused by the backward; lora_A is read in
+    its native [r,K] layout."""
 
     @staticmethod
     def forward(ctx, x, wq, aq, bq, wk, wv, av, bv, scale,
@@ -383,21 +392,21 @@ class QKVProj(torch.autograd.Function):
         yq = torch.nn.functional.linear(x2, wq)
         yk = torch.nn.functional.linear(x2, wk)
         yv = torch.nn.functional.linear(x2, wv)
-        tq = lora_contract(x2, aq, None, seed_q, keep)
-        lora_expand_add(yq, tq, bq, scale)
-        tv = lora_contract(x2, av, None, seed_v, keep)
-        lora_expand_add(yv, tv, bv, scale)
-        ctx.save_for_backward(x2, wq, aq, bq, wk, wv, av, bv, tq, tv)
-        ctx.meta = (scale, seed_q, seed_v, keep, xs)
+        bqt = bq.t().contiguous()                # [r,Nq]
+        bvt = bv.t().contiguous()                # [r,Nv]
+        tq, tv = lora_contract2(x2, aq, av, seed_q, seed_v, keep)
+        lora_expand_add_t(yq, tq, bqt, scale)
+        lora_expand_add_t(yv, tv, bvt, scale)
+        ctx.save_for_backward(x2, wq, aq, bqt, wk, wv, av, bvt, tq, tv)
+        ctx.meta = (scale, seed_q, seed_v, keep, xs, bq.dtype, bv.dtype)
         return (yq.reshape(*xs[:-1], wq.shape[0]),
                 yk.reshape(*xs[:-1], wk.shape[0]),
                 yv.reshape(*xs[:-1], wv.shape[0]))
 
     @staticmethod
     def backward(ctx, dyq, dyk, dyv):
-        from . import lora_wgrad
-        x2, wq, aq, bq, wk, wv, av, bv, tq, tv = ctx.saved_tensors
-        scale, seed_q, seed_v, keep, xs = ctx.meta
+        x2, wq, aq, bqt, wk, wv, av, bvt, tq, tv = ctx.saved_tensors
+        scale, seed_q, seed_v, keep, xs, bq_dtype, bv_dtype = ctx.meta
         dq2 = dyq.reshape(-1, dyq.shape[-1]).contiguous()
         dk2 = dyk.reshape(-1, dyk.shape[-1]).contiguous()
         dv2 = dyv.reshape(-1, dyv.shape[-1]).contiguous()
@@ -405,16 +414,13 @@ class QKVProj(torch.autograd.Function):
         dx.addmm_(dk2, wk)
         dx.addmm_(dv2, wv)
         # LoRA grads + low-rank dx terms (expand_add is in-place on dx)
-        dtq = lora_contract(dq2, bq.t().contiguous())
-        daq = lora_wgrad(dtq, x2, scale, None, seed_q, keep)
+        dtq = lora_contract(dq2, bqt)
+        dtv = lora_contract(dv2, bvt)
         dbq = lora_wgrad(tq, dq2, scale).t().contiguous()
-        lora_expand_add(dx, dtq, aq.t().contiguous(), scale, None,
-                        seed_q, keep)
-        dtv = lora_contract(dv2, bv.t().contiguous())
-        dav = lora_wgrad(dtv, x2, scale, None, seed_v, keep)
         dbv = lora_wgrad(tv, dv2, scale).t().contiguous()
-        lora_expand_add(dx, dtv, av.t().contiguous(), scale, None,
-                        seed_v, keep)
+        daq = lora_wgrad(dtq, x2, scale, None, seed_q, keep)
+        dav = lora_wgrad(dtv, x2, scale, None, seed_v, keep)
+        lora_expand_add2(dx, dtq, dtv, aq, av, scale, seed_q, seed_v, keep)
         return (dx.reshape(xs), None, daq.to(aq.dtype),
-                dbq.to(bq.dtype), None, None, dav.to(av.dtype),
-                dbv.to(bv.dtype), None, None, None, None)
+                dbq.to(bq_dtype), None, None, dav.to(av.dtype),
+                dbv.to(bv_dtype), None, None, None, None)

@@ -31,7 +31,7 @@ void launch_xent_dlogits(const void*, const long*, const float*, void*,
 void launch_adamw(void*, float*, const float*, float*, float*, long, float,
                   float, float, float, float, int, hipStream_t);
 void launch_l2_norm(const float*, float*, float*, long, hipStream_t);
-int lora_contract_ksplit(int K, long M);
+int lora_contract_ksplit(int K, long M, int r);
 void launch_dropout_mask(void*, long, unsigned long long, float,
                          hipStream_t);
 void launch_lora_contract(const void*, const void*, const void*, float*,
@@ -41,6 +41,13 @@ void launch_lora_expand_add(void*, const float*, const void*, const void*,
                             long, int, int, float, unsigned long long,
                             float, hipStream_t);
 int lora_wgrad_splitm(int K, int r, long M);
+void launch_lora_contract2(const void*, const void*, const void*, float*,
+                           float*, long, int, int, unsigned long long,
+                           unsigned long long, float, hipStream_t);
+void launch_lora_expand_add_dual(void*, const float*, const float*,
+                                 const void*, const void*, long, int, int,
+                                 float, unsigned long long,
+                                 unsigned long long, float, hipStream_t);
 void launch_lora_wgrad(const float*, const void*, const void*, float*,
                        float*, long, int, int, float, unsigned long long,
                        float, hipStream_t);
@@ -228,7 +235,7 @@ torch::Tensor lora_contract(torch::Tensor x, torch::Tensor w,
   TORCH_CHECK(r <= 64, "r <= 64");
   TORCH_CHECK(K % 8 == 0);
   auto t = torch::empty({M, r}, x.options().dtype(torch::kFloat));
-  const int nsplit = lora_contract_ksplit(K, M);
+  const int nsplit = lora_contract_ksplit(K, M, r);
   torch::Tensor part;
   float* part_ptr = nullptr;
   if (nsplit > 1) {
@@ -241,6 +248,87 @@ torch::Tensor lora_contract(torch::Tensor x, torch::Tensor w,
                        (unsigned long long)seed, (float)keep,
                        cur_stream());
   return t;
+}
+
+// Two adapters, two dropout seeds, one pass over x: (t0, t1), each
+// bit-identical to lora_contract with its own adapter and seed.
+std::vector<torch::Tensor> lora_contract2(torch::Tensor x, torch::Tensor w0,
+                                          torch::Tensor w1, int64_t seed0,
+                                          int64_t seed1, double keep) {
+  check_bf16_contig(x, "x");
+  check_bf16_contig(w0, "w0");
+  check_bf16_contig(w1, "w1");
+  const int K = (int)x.size(-1);
+  const long M = x.numel() / K;
+  const int r = (int)w0.size(0);
+  TORCH_CHECK(w0.dim() == 2 && w0.sizes() == w1.sizes() && w0.size(1) == K,
+              "w0/w1 [r,K] mismatch");
+  TORCH_CHECK(r >= 1 && r <= 16, "lora_contract2: r <= 16");
+  TORCH_CHECK(K % 8 == 0);
+  auto t = torch::empty({2, M, r}, x.options().dtype(torch::kFloat));
+  const int nsplit = lora_contract_ksplit(K, M, r);
+  torch::Tensor part;
+  float* part_ptr = nullptr;
+  if (nsplit > 1) {
+    part = torch::empty({nsplit, 2, M, r},
+                        x.options().dtype(torch::kFloat));
+    part_ptr = part.data_ptr<float>();
+  }
+  launch_lora_contract2(x.data_ptr(), w0.data_ptr(), w1.data_ptr(),
+                        part_ptr, t.data_ptr<float>(), M, K, r,
+                        (unsigned long long)seed0,
+                        (unsigned long long)seed1, (float)keep,
+                        cur_stream());
+  return {t[0], t[1]};
+}
+
+// wt is the adapter already in [r,N] (lora_B transposed, or lora_A as it
+// is for the dx term): no transposed copy per call.
+void lora_expand_add_t(torch::Tensor y, torch::Tensor t, torch::Tensor wt,
+                       double scale, c10::optional<torch::Tensor> mask,
+                       int64_t seed, double keep) {
+  check_bf16_contig(y, "y");
+  check_bf16_contig(wt, "wt");
+  const int N = (int)y.size(-1);
+  const long M = y.numel() / N;
+  const int r = (int)wt.size(0);
+  TORCH_CHECK(wt.dim() == 2 && wt.size(1) == N, "wt [r,N] mismatch");
+  TORCH_CHECK(t.scalar_type() == torch::kFloat && t.is_contiguous() &&
+              t.numel() == M * r, "t [M,r] f32");
+  TORCH_CHECK(keep >= 1.0 || (r <= 16 && N % 8 == 0 && M >= 64),
+              "RNG dropout needs the r<=16 fast path; materialize the "
+              "mask for this shape");
+  launch_lora_expand_add(y.data_ptr(), t.data_ptr<float>(), wt.data_ptr(),
+                         opt_mask(mask, y.numel(), "mask"), M, N, r,
+                         (float)scale, (unsigned long long)seed,
+                         (float)keep, cur_stream());
+}
+
+// y += mask0 o (s * t0 @ a0) + mask1 o (s * t1 @ a1), a0/a1 [r,N]: one
+// read-modify-write of y, one rounding.
+void lora_expand_add2(torch::Tensor y, torch::Tensor t0, torch::Tensor t1,
+                      torch::Tensor a0, torch::Tensor a1, double scale,
+                      int64_t seed0, int64_t seed1, double keep) {
+  check_bf16_contig(y, "y");
+  check_bf16_contig(a0, "a0");
+  check_bf16_contig(a1, "a1");
+  const int N = (int)y.size(-1);
+  const long M = y.numel() / N;
+  const int r = (int)a0.size(0);
+  TORCH_CHECK(a0.dim() == 2 && a0.sizes() == a1.sizes() && a0.size(1) == N,
+              "a0/a1 [r,N] mismatch");
+  TORCH_CHECK(r >= 1 && r <= 16 && N % 8 == 0,
+              "lora_expand_add2: r <= 16, N % 8 == 0");
+  for (const auto& t : {t0, t1})
+    TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kFloat &&
+                t.is_contiguous() && t.numel() == M * r, "t [M,r] f32");
+  if (M == 0) return;
+  launch_lora_expand_add_dual(y.data_ptr(), t0.data_ptr<float>(),
+                              t1.data_ptr<float>(), a0.data_ptr(),
+                              a1.data_ptr(), M, N, r, (float)scale,
+                              (unsigned long long)seed0,
+                              (unsigned long long)seed1, (float)keep,
+                              cur_stream());
 }
 
 void lora_expand_add(torch::Tensor y, torch::Tensor t, torch::Tensor w,
@@ -655,6 +743,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("lora_wgrad", &lora_wgrad, py::arg("t"), py::arg("x"),
         py::arg("scale"), py::arg("mask") = py::none(),
         py::arg("seed") = 0, py::arg("keep") = 1.0);
+  m.def("lora_contract2", &lora_contract2, py::arg("x"), py::arg("w0"),
+        py::arg("w1"), py::arg("seed0") = 0, py::arg("seed1") = 0,
+        py::arg("keep") = 1.0);
+  m.def("lora_expand_add_t", &lora_expand_add_t, py::arg("y"),
+        py::arg("t"), py::arg("wt"), py::arg("scale"),
+        py::arg("mask") = py::none(), py::arg("seed") = 0,
+        py::arg("keep") = 1.0);
+  m.def("lora_expand_add2", &lora_expand_add2, py::arg("y"), py::arg("t0"),
+        py::arg("t1"), py::arg("a0"), py::arg("a1"), py::arg("scale"),
+        py::arg("seed0") = 0, py::arg("seed1") = 0, py::arg("keep") = 1.0);
   m.def("dropout_mask", &dropout_mask, py::arg("m"), py::arg("k"),
         py::arg("seed"), py::arg("keep"), py::arg("like"));
   m.def("adamw", &adamw);

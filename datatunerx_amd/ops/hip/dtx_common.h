@@ -64,11 +64,12 @@ __device__ __forceinline__ unsigned dtx_cvt_pk_bf16(float lo, float hi) {
 // every kernel that consumes it (contract / wgrad / expand), so the
 // dropout mask is never materialized in HBM. One hash covers 4
 // elements (16 random bits each; keep-prob quantized to 1/65536).
-__device__ __forceinline__ void dtx_dropout4(unsigned long long seed,
-                                             unsigned long long group,
-                                             unsigned thr16, float inv_keep,
-                                             float mv[4]) {
-  unsigned long long z = seed + group * 0x9E3779B97F4A7C15ull;
+#define DTX_RNG_GAMMA 0x9E3779B97F4A7C15ull
+
+// splitmix64 finalizer over z = seed + group * GAMMA -> 4 mask values
+__device__ __forceinline__ void dtx_dropout4_z(unsigned long long z,
+                                               unsigned thr16,
+                                               float inv_keep, float mv[4]) {
   z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
   z ^= z >> 27; z *= 0x94D049BB133111EBull;
   z ^= z >> 31;
@@ -77,13 +78,36 @@ __device__ __forceinline__ void dtx_dropout4(unsigned long long seed,
     mv[i] = ((unsigned)(z >> (16 * i)) & 0xFFFFu) < thr16 ? inv_keep : 0.f;
 }
 
+__device__ __forceinline__ void dtx_dropout4(unsigned long long seed,
+                                             unsigned long long group,
+                                             unsigned thr16, float inv_keep,
+                                             float mv[4]) {
+  dtx_dropout4_z(seed + group * DTX_RNG_GAMMA, thr16, inv_keep, mv);
+}
+
+// The seed-independent half of the counter for an 8-aligned linear
+// offset: kernels that draw two masks for the same elements (two seeds)
+// pay the 64-bit multiply once.
+__device__ __forceinline__ unsigned long long dtx_dropout_ctr(long off) {
+  return (unsigned long long)(off >> 2) * DTX_RNG_GAMMA;
+}
+
+// 8 mask values from a precomputed counter; the second group's counter
+// is ctr + GAMMA (exact mod 2^64), so no second multiply either.
+__device__ __forceinline__ void dtx_dropout8_ctr(unsigned long long seed,
+                                                 unsigned long long ctr,
+                                                 unsigned thr16,
+                                                 float inv_keep,
+                                                 float mv[8]) {
+  dtx_dropout4_z(seed + ctr, thr16, inv_keep, mv);
+  dtx_dropout4_z(seed + ctr + DTX_RNG_GAMMA, thr16, inv_keep, mv + 4);
+}
+
 // 8-element convenience over an 8-aligned linear offset
 __device__ __forceinline__ void dtx_dropout8(unsigned long long seed,
                                              long off, unsigned thr16,
                                              float inv_keep, float mv[8]) {
-  dtx_dropout4(seed, (unsigned long long)(off >> 2), thr16, inv_keep, mv);
-  dtx_dropout4(seed, (unsigned long long)(off >> 2) + 1, thr16, inv_keep,
-               mv + 4);
+  dtx_dropout8_ctr(seed, dtx_dropout_ctr(off), thr16, inv_keep, mv);
 }
 
 // ---- wave/block reductions (64-wide wave) ----

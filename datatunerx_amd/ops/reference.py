@@ -288,6 +288,41 @@ def lora_wgrad(t: torch.Tensor, x: torch.Tensor, scale: float = 1.0,
     return scale * (t.float().t() @ _masked(x2, mask).float())
 
 
+# Dual forms (two adapters sharing one activation, e.g. the q and v LoRA
+# pairs of one attention input): CPU twins of the one-pass GPU ops.
+def lora_contract2(x: torch.Tensor, w0: torch.Tensor, w1: torch.Tensor,
+                   seed0: int = 0, seed1: int = 0, keep: float = 1.0):
+    """(t0, t1) = ((x o mask0) @ w0^T, (x o mask1) @ w1^T): exactly two
+    lora_contract calls (the GPU op reads x once)."""
+    return (lora_contract(x, w0, None, seed0, keep),
+            lora_contract(x, w1, None, seed1, keep))
+
+
+def lora_expand_add_t(y: torch.Tensor, t: torch.Tensor, wt: torch.Tensor,
+                      scale: float, mask=None, seed: int = 0,
+                      keep: float = 1.0):
+    """lora_expand_add with the adapter already transposed: wt [r,N]."""
+    return lora_expand_add(y, t, wt.t(), scale, mask, seed, keep)
+
+
+def lora_expand_add2(y: torch.Tensor, t0: torch.Tensor, t1: torch.Tensor,
+                     a0: torch.Tensor, a1: torch.Tensor, scale: float,
+                     seed0: int = 0, seed1: int = 0, keep: float = 1.0):
+    """y[M,N] += mask0 o (s * t0 @ a0) + mask1 o (s * t1 @ a1) in place,
+    a0/a1 [r,N]. Both terms are summed with y in fp32 and rounded ONCE
+    (two lora_expand_add calls round y in between)."""
+    y2 = y.reshape(-1, y.shape[-1])
+    acc = y2.float()
+    for t, a, seed in ((t0, a0, seed0), (t1, a1, seed1)):
+        d = scale * (t.float() @ a.float())
+        mask = _resolve_mask(None, seed, keep, y2.shape, y.device, y.dtype)
+        if mask is not None:
+            d = d * mask.float()
+        acc = acc + d
+    y2.copy_(acc.to(y.dtype))
+    return y
+
+
 # ------------------------------------------------------------ fused AdamW
 def adamw_step(p_bf16: torch.Tensor, master: torch.Tensor,
                grad: torch.Tensor, m: torch.Tensor, v: torch.Tensor,

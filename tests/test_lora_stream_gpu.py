@@ -1,0 +1,197 @@
+"""GPU tests for the streaming LoRA path: the r <= 16 contract kernel on
+every plan the dispatch can return, and the dual (two adapters, one
+pass) contract / expand-add ops that QKVProj uses.
+
+Conventions and the 2e-2 bound are those of tests/test_ops_gpu.py; the
+references are ops/reference.py on the CPU. Where the issue promises
+bit-identity (mask mode vs seed mode, dual vs two single calls) the
+assertion is torch.equal.
+"""
+
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+if torch.cuda.is_available():
+    from datatunerx_amd import ops
+    from datatunerx_amd.ops import reference as ref
+    DEV = torch.device("cuda:0")
+    assert ops.have_ext(), "HIP extension must be built for GPU tests"
+
+
+def mk(gen, *shape, dtype=torch.bfloat16, scale=1.0):
+    return (torch.randn(*shape, generator=gen, dtype=torch.float32)
+            .mul(scale).to(dtype).to(DEV))
+
+
+def gen(seed):
+    return torch.Generator().manual_seed(seed)
+
+
+def assert_close(got, want, rtol=2e-2, name=""):
+    got, want = got.float(), want.float()
+    denom = want.abs().max().clamp(min=1e-3)
+    err = (got - want).abs().max() / denom
+    assert err < rtol, f"{name}: rel err {err:.4f} (max {denom:.3f})"
+
+
+# ---------------------------------------------------------------- contract
+# Plans (lora_contract_ksplit, a function of M, K, r):
+#   r <= 16, K <= 1024       streaming kernel writes the output itself
+#   r <= 16, K  > 1024       streaming kernel, ceil(K/1024) partial planes
+#                            (K = 5120, 11008: last slice short; K = 64:
+#                            a slice shorter than one 8-step load batch)
+#   r <= 8 / r <= 16         8- and 16-row LDS tiles
+#   r  > 16, M  < 32768      32x32 kernel, split-K
+#   r  > 16, M >= 32768      32x32 kernel, one slice, k-chunk loop
+CONTRACT_SHAPES = [(32768 + 33, 256, 8), (513, 4096, 16), (33, 5120, 8),
+                   (256, 11008, 8), (64, 64, 4), (512, 2048, 64),
+                   (32768 + 33, 256, 64), (40, 1032, 12)]
+
+
+@pytest.mark.parametrize("M,K,r", CONTRACT_SHAPES)
+def test_contract_all_plans_and_modes(M, K, r):
+    g = gen(M + K + r)
+    x, w = mk(g, M, K, scale=0.3), mk(g, r, K, scale=0.3)
+    t = ops.lora_contract(x, w)
+    assert t.shape == (M, r) and t.dtype == torch.float32
+    assert_close(t.cpu(), ref.lora_contract(x.cpu(), w.cpu()),
+                 name="contract none")
+
+    seed, keep = 4321 + r, 0.9
+    mask = ops.dropout_mask(M, K, seed, keep, x)
+    t_mask = ops.lora_contract(x, w, mask)
+    t_seed = ops.lora_contract(x, w, seed=seed, keep=keep)
+    assert torch.equal(t_mask, t_seed), "contract mask mode != seed mode"
+    assert_close(t_mask.cpu(),
+                 ref.lora_contract(x.cpu(), w.cpu(), mask.cpu()),
+                 name="contract mask")
+
+
+@pytest.mark.parametrize("M,K", [(513, 4096), (32768 + 33, 256)])
+@pytest.mark.parametrize("r", [8, 16])
+@pytest.mark.parametrize("keep", [1.0, 0.9])
+def test_dual_contract_bitwise(M, K, r, keep):
+    g = gen(7 * M + K + r)
+    x = mk(g, M, K, scale=0.3)
+    w0, w1 = mk(g, r, K, scale=0.3), mk(g, r, K, scale=0.3)
+    s0, s1 = 1111, 987654321
+    t0, t1 = ops.lora_contract2(x, w0, w1, s0, s1, keep)
+    assert torch.equal(t0, ops.lora_contract(x, w0, seed=s0, keep=keep))
+    assert torch.equal(t1, ops.lora_contract(x, w1, seed=s1, keep=keep))
+    if keep < 1.0:
+        assert not torch.equal(
+            t1, ops.lora_contract(x, w1, seed=s0, keep=keep)), \
+            "the second adapter must use the second seed"
+
+
+# ------------------------------------------------------------------- wgrad
+# (No dual wgrad: the one-pass kernel measured slower than two
+# lora_wgrad calls and was not kept — profiles/README.md. The wgrad's
+# seed mode shares the RNG counter helper the dual kernels use, so its
+# bits are pinned here against the mask mode and the reference.)
+@pytest.mark.parametrize("M,K,r", [(1024, 4096, 8), (513, 2048, 16)])
+def test_wgrad_seed_mode_bits(M, K, r):
+    g = gen(M + 3 * K + r)
+    x = mk(g, M, K, scale=0.3)
+    t = torch.randn(M, r, generator=g).to(DEV)
+    seed, keep = 55555, 0.9
+    mask = ops.dropout_mask(M, K, seed, keep, x)
+    assert torch.equal(mask.cpu(), ref.dropout_mask(M, K, seed, keep))
+    d = ops.lora_wgrad(t, x, 0.7, seed=seed, keep=keep)
+    assert torch.equal(d, ops.lora_wgrad(t, x, 0.7, mask))
+    assert_close(d.cpu(), ref.lora_wgrad(t.cpu(), x.cpu(), 0.7, mask.cpu()),
+                 name="wgrad seed")
+
+
+# -------------------------------------------------------------- expand-add
+@pytest.mark.parametrize("M,N,r", [(1024, 4096, 8), (511, 1024, 16),
+                                   (37, 264, 4)])
+@pytest.mark.parametrize("keep", [1.0, 0.9])
+def test_dual_expand_add(M, N, r, keep):
+    g = gen(M + N + 5 * r)
+    y = mk(g, M, N)
+    t0 = torch.randn(M, r, generator=g).to(DEV)
+    t1 = torch.randn(M, r, generator=g).to(DEV)
+    a0, a1 = mk(g, r, N, scale=0.3), mk(g, r, N, scale=0.3)
+    s0, s1 = 3333, 424242
+    y_ref = ref.lora_expand_add2(y.cpu().clone(), t0.cpu(), t1.cpu(),
+                                 a0.cpu(), a1.cpu(), 0.5, s0, s1, keep)
+    out = ops.lora_expand_add2(y, t0, t1, a0, a1, 0.5, s0, s1, keep)
+    assert out is y
+    assert_close(y.cpu(), y_ref, name="dual expand")
+
+
+def test_expand_add_t_matches_expand_add():
+    g = gen(99)
+    M, N, r = 512, 2048, 8
+    y = mk(g, M, N)
+    y2 = y.clone()
+    t = torch.randn(M, r, generator=g).to(DEV)
+    b = mk(g, N, r, scale=0.3)
+    ops.lora_expand_add(y, t, b, 0.5, seed=7, keep=0.9)
+    ops.lora_expand_add_t(y2, t, b.t().contiguous(), 0.5, seed=7, keep=0.9)
+    assert torch.equal(y, y2)
+
+
+# ------------------------------------------------------ QKVProj end to end
+def _composed_qkv(x, wq, aq, bq, wk, wv, av, bv, scale, sq, sv, keep,
+                  dyq, dyk, dyv):
+    """The same node out of the three single-adapter ops (what QKVProj
+    ran before the dual ops): outputs and the five gradients."""
+    F = torch.nn.functional
+    x2 = x.reshape(-1, x.shape[-1])
+    yq, yk, yv = F.linear(x2, wq), F.linear(x2, wk), F.linear(x2, wv)
+    tq = ops.lora_contract(x2, aq, None, sq, keep)
+    ops.lora_expand_add(yq, tq, bq, scale)
+    tv = ops.lora_contract(x2, av, None, sv, keep)
+    ops.lora_expand_add(yv, tv, bv, scale)
+    dx = dyq @ wq
+    dx.addmm_(dyk, wk)
+    dx.addmm_(dyv, wv)
+    dtq = ops.lora_contract(dyq, bq.t().contiguous())
+    daq = ops.lora_wgrad(dtq, x2, scale, None, sq, keep)
+    dbq = ops.lora_wgrad(tq, dyq, scale).t().contiguous()
+    ops.lora_expand_add(dx, dtq, aq.t().contiguous(), scale, None, sq, keep)
+    dtv = ops.lora_contract(dyv, bv.t().contiguous())
+    dav = ops.lora_wgrad(dtv, x2, scale, None, sv, keep)
+    dbv = ops.lora_wgrad(tv, dyv, scale).t().contiguous()
+    ops.lora_expand_add(dx, dtv, av.t().contiguous(), scale, None, sv, keep)
+    return (yq, yk, yv), (dx, daq, dbq, dav, dbv)
+
+
+@pytest.mark.parametrize("nkv", [256, 64])          # MHA and GQA widths
+def test_qkvproj_matches_composed_single_ops(nkv):
+    from datatunerx_amd.ops.autograd import QKVProj
+    g = gen(2024 + nkv)
+    B, S, E, r = 2, 100, 256, 8
+    scale, sq, sv, keep = 2.0, 1234567, 7654321, 0.9
+    x = mk(g, B, S, E).requires_grad_(True)
+    wq, wk, wv = (mk(g, E, E, scale=0.06), mk(g, nkv, E, scale=0.06),
+                  mk(g, nkv, E, scale=0.06))
+    aq = mk(g, r, E, scale=0.1).requires_grad_(True)
+    av = mk(g, r, E, scale=0.1).requires_grad_(True)
+    bq = mk(g, E, r, scale=0.1).requires_grad_(True)      # non-zero B
+    bv = mk(g, nkv, r, scale=0.1).requires_grad_(True)
+    dyq, dyk, dyv = mk(g, B * S, E), mk(g, B * S, nkv), mk(g, B * S, nkv)
+
+    q, k, v = QKVProj.apply(x, wq, aq, bq, wk, wv, av, bv, scale, sq, sv,
+                            keep)
+    torch.autograd.backward(
+        [q, k, v], [dyq.view_as(q), dyk.view_as(k), dyv.view_as(v)])
+
+    with torch.no_grad():
+        (yq, yk, yv), (dx, daq, dbq, dav, dbv) = _composed_qkv(
+            x.detach(), wq, aq.detach(), bq.detach(), wk, wv, av.detach(),
+            bv.detach(), scale, sq, sv, keep, dyq, dyk, dyv)
+
+    assert_close(q.reshape(B * S, -1), yq, name="q")
+    assert torch.equal(k.reshape(B * S, -1), yk)
+    assert_close(v.reshape(B * S, -1), yv, name="v")
+    assert_close(x.grad.reshape(B * S, -1), dx, name="dx")
+    assert_close(bq.grad, dbq, name="dbq")
+    assert_close(bv.grad, dbv, name="dbv")
+    # same dt, same x, same seeds, same split plan: bitwise
+    assert torch.equal(aq.grad, daq.to(aq.dtype)), "daq not bitwise"
+    assert torch.equal(av.grad, dav.to(av.dtype)), "dav not bitwise"
