@@ -20,7 +20,7 @@ from ..ops import rope_tables
 from ..ops.autograd import (PairedFrozenGemm, QKVProj, attention,
                             cross_entropy, rmsnorm, rmsnorm_tap,
                             rope, swiglu)
-from .lora import FrozenLinear, LoRALinearModule
+from .lora import FrozenLinear, LoRALinearModule, draw_dropout_seed
 from .multilora import MultiLoRALinear
 
 
@@ -177,8 +177,8 @@ class LlamaAttention(nn.Module):
             keep, sq, sv = 1.0, 0, 0
             if self.training and qm.dropout > 0.0:
                 keep = 1.0 - qm.dropout
-                sq = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
-                sv = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
+                sq = draw_dropout_seed()
+                sv = draw_dropout_seed()
             q, k, v = QKVProj.apply(x, qm.weight, qm.lora_A, qm.lora_B,
                                     km.weight, vm.weight, vm.lora_A,
                                     vm.lora_B, qm.scale, sq, sv, keep)

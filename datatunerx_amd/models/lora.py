@@ -19,7 +19,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from ..ops import gemm_nt_supported, lora_contract, lora_expand_add
+from ..ops import gemm_nt_supported
 from ..ops.autograd import FrozenGemm
 from ..ops.autograd import LoRALinear as _FusedLoRAFn
 
@@ -85,49 +85,19 @@ class FrozenLinear(nn.Module):
         return F.linear(x, self.weight)
 
 
-class LoRAFunctionWithDropout(torch.autograd.Function):
-    """Fused LoRA linear with PEFT-style input dropout on the low-rank
-    path. The dropout mask is applied INSIDE the contract/wgrad/expand
-    kernels; with `seed`-mode (r <= 16, the default ranks) it is
-    RE-GENERATED from a counter-based RNG in each kernel and never
-    touches HBM at all — no bernoulli launch, no mask reads. `mask` is
-    the materialized-tensor fallback (r > 16 / CPU-provided masks).
-    """
-
-    @staticmethod
-    def forward(ctx, x, w, a, b, scale, mask, seed, keep, wt=None):
-        from ..ops.autograd import _base_gemm
-        xs = x.shape
-        x2 = x.reshape(-1, xs[-1])
-        y = _base_gemm(x2, w, wt)
-        t = lora_contract(x2, a, mask, seed, keep)   # (x o mask) @ A^T
-        lora_expand_add(y, t, b, scale)
-        ctx.save_for_backward(x2, w, a, b, t, mask, wt)
-        ctx.scale, ctx.xshape = scale, xs
-        ctx.seed, ctx.keep = seed, keep
-        return y.reshape(*xs[:-1], w.shape[0])
-
-    @staticmethod
-    def backward(ctx, dy):
-        from ..ops import gemm_nt, lora_wgrad
-        x2, w, a, b, t, mask, wt = ctx.saved_tensors
-        s, seed, keep = ctx.scale, ctx.seed, ctx.keep
-        dy2 = dy.reshape(-1, dy.shape[-1]).contiguous()
-        dx = gemm_nt(dy2, wt) if (wt is not None and dy2.is_cuda) \
-            else dy2 @ w
-        dt = lora_contract(dy2, b.t().contiguous())       # [M,r] = dy @ B
-        da = lora_wgrad(dt, x2, s, mask, seed, keep)  # dt^T @ (x o mask)
-        db = lora_wgrad(t, dy2, s).t().contiguous()
-        # dx += mask o (s * dt @ A)
-        lora_expand_add(dx, dt, a.t().contiguous(), s, mask, seed, keep)
-        return (dx.reshape(ctx.xshape), None, da.to(a.dtype),
-                db.to(b.dtype), None, None, None, None, None)
+def draw_dropout_seed() -> int:
+    """Per-call seed of the fused LoRA dropout, drawn from torch's
+    generator so dropout stays reproducible under torch.manual_seed."""
+    return int(torch.randint(0, 2**31 - 1, (1,)).item())
 
 
 class LoRALinearModule(nn.Module):
     """Frozen base weight + trainable LoRA A/B (HF layouts: A [r,in],
     B [out,r]); scale = alpha / r (reference defaults r=8 alpha=32 —
-    cmd/tuning/parser.py:138-149)."""
+    cmd/tuning/parser.py:138-149). Training with dropout > 0 hands the
+    fused node one (seed, keep) per call; how the mask reaches each
+    kernel is decided in the op layer (ops.lora_expand_add_t), never
+    here."""
 
     def __init__(self, in_features: int, out_features: int, r: int = 8,
                  alpha: float = 32.0, dropout: float = 0.0,
@@ -145,24 +115,11 @@ class LoRALinearModule(nn.Module):
 
     def forward(self, x):
         wt = _weight_t(self) if x.is_cuda else None
-        if not (self.training and self.dropout > 0.0):
-            return _FusedLoRAFn.apply(x, self.weight, self.lora_A,
-                                      self.lora_B, self.scale, wt)
-        keep = 1.0 - self.dropout
-        # draw the per-call RNG seed from torch's generator so dropout
-        # stays reproducible under torch.manual_seed
-        seed = int(torch.randint(0, 2**31 - 1, (1,)).item())
-        if self.r <= 16 and self.in_features % 8 == 0:
-            # fused counter-based RNG: mask never materialized
-            return LoRAFunctionWithDropout.apply(
-                x, self.weight, self.lora_A, self.lora_B, self.scale,
-                None, seed, keep, wt)
-        from ..ops import dropout_mask
-        mask = dropout_mask(x.numel() // x.shape[-1], x.shape[-1], seed,
-                            keep, x).to(x.dtype)
-        return LoRAFunctionWithDropout.apply(x, self.weight, self.lora_A,
-                                             self.lora_B, self.scale,
-                                             mask, 0, 1.0, wt)
+        seed, keep = 0, 1.0
+        if self.training and self.dropout > 0.0:
+            seed, keep = draw_dropout_seed(), 1.0 - self.dropout
+        return _FusedLoRAFn.apply(x, self.weight, self.lora_A, self.lora_B,
+                                  self.scale, wt, seed, keep)
 
     def merged_weight(self):
         """W + s·B@A — used by the serving engine (no adapter overhead)."""

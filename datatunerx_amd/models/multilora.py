@@ -193,8 +193,7 @@ class MultiLoRALinear(nn.Module):
             if xb.is_cuda:
                 xb = xb.contiguous()
             t = ops.lora_contract(xb, self.A[g])
-            ops.lora_expand_add(yb, t, self.Bt[g].t().contiguous(),
-                                self.scales_host[g])
+            ops.lora_expand_add_t(yb, t, self.Bt[g], self.scales_host[g])
         else:
             d = (xb.float() @ self.A[g].float().t()) @ self.Bt[g].float()
             yb.add_((self.scales_host[g] * d).to(yb.dtype))

@@ -213,9 +213,10 @@ def lora_contract(x, w, mask=None, seed: int = 0, keep: float = 1.0):
 
 def lora_expand_add(y, t, w, scale: float, mask=None, seed: int = 0,
                     keep: float = 1.0):
+    """lora_expand_add_t for an adapter in the PEFT layout, w [N,r]."""
     if _gpu(y):
-        _EXT.lora_expand_add(y, t, w, scale, mask, seed, keep)
-        return y
+        return lora_expand_add_t(y, t, w.t().contiguous(), scale, mask,
+                                 seed, keep)
     return ref.lora_expand_add(y, t, w, scale, mask, seed, keep)
 
 
@@ -245,8 +246,18 @@ def lora_contract2(x, w0, w1, seed0: int = 0, seed1: int = 0,
 
 def lora_expand_add_t(y, t, wt, scale: float, mask=None, seed: int = 0,
                       keep: float = 1.0):
-    """lora_expand_add with the adapter already in [r,N]."""
+    """In place: y[M,N] += (mask o) scale * t[M,r] @ wt[r,N].
+
+    The one place that picks the dropout mode of the expand-add on the
+    GPU: seed mode runs in the kernel where it has an RNG mode
+    (lora_expand_rng_ok); for the other shapes the same bits are
+    materialized with dropout_mask and the kernel runs in mask mode."""
     if _gpu(y):
+        N = y.shape[-1]
+        M = y.numel() // N
+        if (mask is None and keep < 1.0
+                and not _EXT.lora_expand_rng_ok(M, N, wt.shape[0])):
+            mask, seed, keep = dropout_mask(M, N, seed, keep, y), 0, 1.0
         _EXT.lora_expand_add_t(y, t, wt, scale, mask, seed, keep)
         return y
     return ref.lora_expand_add_t(y, t, wt, scale, mask, seed, keep)
@@ -265,8 +276,9 @@ def lora_expand_add2(y, t0, t1, a0, a1, scale: float, seed0: int = 0,
 
 def dropout_mask(M: int, K: int, seed: int, keep: float, like):
     """Materialize the RNG mask (bit-identical to the fused kernels'
-    in-kernel bits) — tests and the r>16 fallback path."""
-    if like.is_cuda and _EXT is not None:
+    in-kernel bits) — tests and the expand-add shapes without an RNG
+    mode (lora_expand_add_t)."""
+    if _gpu(like):
         return _EXT.dropout_mask(M, K, seed, keep, like)
     return ref.dropout_mask(M, K, seed, keep, device=like.device,
                             dtype=torch.bfloat16)

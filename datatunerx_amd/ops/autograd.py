@@ -11,9 +11,9 @@ import os
 import torch
 
 from . import (attn_bwd, attn_fwd, lora_contract, lora_contract2,
-               lora_expand_add, lora_expand_add2, lora_expand_add_t,
-               lora_wgrad, rmsnorm_bwd, rmsnorm_fwd, rope_bwd, rope_fwd,
-               softmax_xent_bwd, softmax_xent_fwd, swiglu_bwd, swiglu_fwd)
+               lora_expand_add2, lora_expand_add_t, lora_wgrad, rmsnorm_bwd,
+               rmsnorm_fwd, rope_bwd, rope_fwd, softmax_xent_bwd,
+               softmax_xent_fwd, swiglu_bwd, swiglu_fwd)
 
 
 class RMSNorm(torch.autograd.Function):
@@ -186,48 +186,57 @@ def _base_gemm(x2, w, wt):
 
 
 class LoRALinear(torch.autograd.Function):
-    """y = x @ W^T + scale * (x @ A^T) @ B^T  with frozen W.
+    """y = x @ W^T + scale * (dropout(x) @ A^T) @ B^T  with frozen W.
 
     W: [N,K] (frozen base, no wgrad) — the base GEMM is the hand-written
     gfx950 MFMA kernel (ops/hip/gemm.hip) with `wt` = W^T cached so the
     dgrad dx = dy @ W is the same contraction-contiguous NT kernel; the
     low-rank path is the fused HIP contract/expand pair. A: [r,K],
     B: [N,r] (HF PEFT adapter layout, the checkpoint-compat contract —
-    SURVEY.md §5 Checkpoint/resume).
+    SURVEY.md §5 Checkpoint/resume). B is transposed once here and the
+    copy reused by the backward; A is read as it is.
+
+    PEFT-style input dropout on the low-rank path is (seed, keep < 1):
+    the mask is a counter-based function of (seed, element offset) that
+    contract, wgrad and expand-add each regenerate in-kernel, so forward
+    and backward agree and it never touches HBM. This node does not pick
+    a dropout mode; ops.lora_expand_add_t materializes the mask for the
+    shapes whose kernel has no RNG mode.
     """
 
     @staticmethod
-    def forward(ctx, x, w, a, b, scale, wt=None):
+    def forward(ctx, x, w, a, b, scale, wt=None, seed=0, keep=1.0):
         xs = x.shape
         x2 = x.reshape(-1, xs[-1])
-        if x2.is_cuda and x2.shape[0] == 1:
+        if x2.is_cuda and x2.shape[0] == 1 and keep >= 1.0:
             from . import gemv
             y = gemv(x2, w)                      # decode: streaming GEMV
         else:
             y = _base_gemm(x2, w, wt)
-        t = lora_contract(x2, a)                 # [M,r] f32
-        lora_expand_add(y, t, b, scale)          # y += s * t @ B^T
-        ctx.save_for_backward(x2, w, a, b, t, wt)
-        ctx.scale = scale
-        ctx.xshape = xs
+        bt = b.t().contiguous()                  # [r,N]
+        t = lora_contract(x2, a, None, seed, keep)   # (x o mask) @ A^T
+        lora_expand_add_t(y, t, bt, scale)       # y += s * t @ B^T
+        ctx.save_for_backward(x2, w, a, bt, t, wt)
+        ctx.meta = (scale, seed, keep, xs, b.dtype)
         return y.reshape(*xs[:-1], w.shape[0])
 
     @staticmethod
     def backward(ctx, dy):
-        x2, w, a, b, t, wt = ctx.saved_tensors
-        s = ctx.scale
+        x2, w, a, bt, t, wt = ctx.saved_tensors
+        s, seed, keep, xs, b_dtype = ctx.meta
         dy2 = dy.reshape(-1, dy.shape[-1]).contiguous()
         if wt is not None and dy2.is_cuda:
             from . import gemm_nt
             dx = gemm_nt(dy2, wt)                # base dgrad (NT MFMA)
         else:
             dx = dy2 @ w
-        dt = lora_contract(dy2, b.t().contiguous())   # [M,r] = dy @ B
-        db = lora_wgrad(t, dy2, s)                    # [r,N] -> B grad is [N,r]
-        da = lora_wgrad(dt, x2, s)                    # [r,K]
-        lora_expand_add(dx, dt, a.t().contiguous(), s)  # dx += s * dt @ A
-        return (dx.reshape(ctx.xshape), None, da.to(a.dtype),
-                db.t().contiguous().to(b.dtype), None, None)
+        dt = lora_contract(dy2, bt)                   # [M,r] = dy @ B
+        db = lora_wgrad(t, dy2, s).t().contiguous()   # [r,N] -> B is [N,r]
+        da = lora_wgrad(dt, x2, s, None, seed, keep)  # dt^T @ (x o mask)
+        # dx += mask o (s * dt @ A)
+        lora_expand_add_t(dx, dt, a, s, None, seed, keep)
+        return (dx.reshape(xs), None, da.to(a.dtype), db.to(b_dtype),
+                None, None, None, None)
 
 
 def lora_linear(x, w, a, b, scale: float, wt=None):

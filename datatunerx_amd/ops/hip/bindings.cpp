@@ -40,6 +40,7 @@ void launch_lora_contract(const void*, const void*, const void*, float*,
 void launch_lora_expand_add(void*, const float*, const void*, const void*,
                             long, int, int, float, unsigned long long,
                             float, hipStream_t);
+bool lora_expand_rng_ok(long M, int N, int r);
 int lora_wgrad_splitm(int K, int r, long M);
 void launch_lora_contract2(const void*, const void*, const void*, float*,
                            float*, long, int, int, unsigned long long,
@@ -295,7 +296,7 @@ void lora_expand_add_t(torch::Tensor y, torch::Tensor t, torch::Tensor wt,
   TORCH_CHECK(wt.dim() == 2 && wt.size(1) == N, "wt [r,N] mismatch");
   TORCH_CHECK(t.scalar_type() == torch::kFloat && t.is_contiguous() &&
               t.numel() == M * r, "t [M,r] f32");
-  TORCH_CHECK(keep >= 1.0 || (r <= 16 && N % 8 == 0 && M >= 64),
+  TORCH_CHECK(keep >= 1.0 || lora_expand_rng_ok(M, N, r),
               "RNG dropout needs the r<=16 fast path; materialize the "
               "mask for this shape");
   launch_lora_expand_add(y.data_ptr(), t.data_ptr<float>(), wt.data_ptr(),
@@ -329,26 +330,6 @@ void lora_expand_add2(torch::Tensor y, torch::Tensor t0, torch::Tensor t1,
                               (unsigned long long)seed0,
                               (unsigned long long)seed1, (float)keep,
                               cur_stream());
-}
-
-void lora_expand_add(torch::Tensor y, torch::Tensor t, torch::Tensor w,
-                     double scale, c10::optional<torch::Tensor> mask,
-                     int64_t seed, double keep) {
-  check_bf16_contig(y, "y");
-  check_bf16_contig(w, "w");
-  const int N = (int)y.size(-1);
-  const long M = y.numel() / N;
-  const int r = (int)w.size(1);
-  TORCH_CHECK(w.size(0) == N, "w [N,r] mismatch");
-  TORCH_CHECK(t.scalar_type() == torch::kFloat && t.is_contiguous());
-  auto wt = w.t().contiguous();          // [r,N] for coalesced rows
-  TORCH_CHECK(keep >= 1.0 || (r <= 16 && N % 8 == 0 && M >= 64),
-              "RNG dropout needs the r<=16 fast path; materialize the "
-              "mask for this shape");
-  launch_lora_expand_add(y.data_ptr(), t.data_ptr<float>(), wt.data_ptr(),
-                         opt_mask(mask, y.numel(), "mask"), M, N, r,
-                         (float)scale, (unsigned long long)seed,
-                         (float)keep, cur_stream());
 }
 
 torch::Tensor lora_wgrad(torch::Tensor t, torch::Tensor x, double scale,
@@ -737,9 +718,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("lora_contract", &lora_contract, py::arg("x"), py::arg("w"),
         py::arg("mask") = py::none(), py::arg("seed") = 0,
         py::arg("keep") = 1.0);
-  m.def("lora_expand_add", &lora_expand_add, py::arg("y"), py::arg("t"),
-        py::arg("w"), py::arg("scale"), py::arg("mask") = py::none(),
-        py::arg("seed") = 0, py::arg("keep") = 1.0);
   m.def("lora_wgrad", &lora_wgrad, py::arg("t"), py::arg("x"),
         py::arg("scale"), py::arg("mask") = py::none(),
         py::arg("seed") = 0, py::arg("keep") = 1.0);
@@ -750,6 +728,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("t"), py::arg("wt"), py::arg("scale"),
         py::arg("mask") = py::none(), py::arg("seed") = 0,
         py::arg("keep") = 1.0);
+  m.def("lora_expand_rng_ok", &lora_expand_rng_ok, py::arg("m"),
+        py::arg("n"), py::arg("r"));
   m.def("lora_expand_add2", &lora_expand_add2, py::arg("y"), py::arg("t0"),
         py::arg("t1"), py::arg("a0"), py::arg("a1"), py::arg("scale"),
         py::arg("seed0") = 0, py::arg("seed1") = 0, py::arg("keep") = 1.0);

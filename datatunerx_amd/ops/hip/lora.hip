@@ -218,6 +218,10 @@ void lora_contract_kernel(const unsigned short* __restrict__ X,
           short8v xf = xrow < M
               ? *reinterpret_cast<const short8v*>(xp + kc + hi * 8)
               : short8v{0, 0, 0, 0, 0, 0, 0, 0};
+          // The operations of lora_mask_bf16 / lora_mask_f32, kept
+          // written out: through the helpers this kernel takes two more
+          // VGPRs (MODE 1: 62 -> 64; MODE 2: 64 -> 66, one wave per
+          // SIMD less).
           if (MODE == 1 && mp) {
             short8v mf = *reinterpret_cast<const short8v*>(
                 mp + kc + hi * 8);
@@ -264,9 +268,10 @@ void lora_contract_kernel(const unsigned short* __restrict__ X,
 }
 
 // -------------------------------------------------------------- expand_add
-// Y[M,N] += (mask o) s * T[M,r] @ WT[r,N].  WT is the PRE-TRANSPOSED
-// adapter (binding does w.t().contiguous(): 64 KB, L1/L2-resident), so
-// every access here is a coalesced 16-byte load — no LDS staging pass.
+// Y[M,N] += (mask o) s * T[M,r] @ WT[r,N].  WT is the adapter in [r,N]
+// (lora_A as it is; lora_B transposed by the caller, once per forward:
+// 64 KB, L1/L2-resident), so every access here is a coalesced 16-byte
+// load — no LDS staging pass.
 // j blocked by 8 so register pressure is independent of r.
 template <bool MASKED>
 __global__ __launch_bounds__(DTX_BLOCK)
@@ -580,6 +585,32 @@ static void dropout_spec(float keep, unsigned* thr16, float* inv_keep) {
   *inv_keep = x.f;
 }
 
+// The kernels' MODE template argument and the RNG constants, from what a
+// launcher is given: 1 = bf16 mask tensor Mk (it wins over keep),
+// 2 = in-kernel RNG (keep < 1 and no Mk), 0 = no dropout.
+struct LoraDropout {
+  int mode;
+  unsigned thr16 = 0;
+  float inv_keep = 1.f;
+  LoraDropout(const void* Mk, float keep)
+      : mode(Mk ? 1 : keep < 1.f ? 2 : 0) {
+    if (mode == 2) dropout_spec(keep, &thr16, &inv_keep);
+  }
+};
+// LAUNCH(MODE) with d.mode as the compile-time MODE
+#define LORA_MODE_SWITCH(d, LAUNCH)                                       \
+  do {                                                                    \
+    if ((d).mode == 1) LAUNCH(1);                                         \
+    else if ((d).mode == 2) LAUNCH(2);                                    \
+    else LAUNCH(0);                                                       \
+  } while (0)
+
+// Shapes lora_expand_add_kernel2 takes; the v1 kernel that takes the
+// rest has no RNG mode (the ops layer materializes the mask for it).
+bool lora_expand_rng_ok(long M, int N, int r) {
+  return r <= 16 && N % 8 == 0 && M >= 64;
+}
+
 // ------------------------------------------------------------- launchers
 void launch_reduce_partials(const float* part, float* out, int P, long L,
                             hipStream_t s);
@@ -636,24 +667,21 @@ static void launch_contract_stream(const void* X, const void* W0,
   if (gx < 1) gx = 1;
   dim3 grid((int)gx, nsplit);
   float* dst = nsplit > 1 ? part : out;
-  unsigned thr16 = 0; float ik = 1.f;
-  const bool rng = !Mk && keep < 1.f;
-  if (rng) dropout_spec(keep, &thr16, &ik);
+  const LoraDropout d(Mk, keep);
 #define STREAM(RP, MODE, NA)                                              \
   lora_contract_stream_kernel<RP, MODE, NA><<<grid, DTX_BLOCK, 0, s>>>(   \
       (const unsigned short*)X, (const unsigned short*)W0,                \
       (const unsigned short*)W1, (const unsigned short*)Mk, dst, M, K, r, \
-      seed0, seed1, thr16, ik)
-#define STREAM_M(RP)                                                      \
-  do {                                                                    \
-    if (na == 2) { if (rng) STREAM(RP, 2, 2); else STREAM(RP, 0, 2); }    \
-    else if (Mk) STREAM(RP, 1, 1);                                        \
-    else if (rng) STREAM(RP, 2, 1);                                       \
-    else STREAM(RP, 0, 1);                                                \
-  } while (0)
-  if (r <= 8) STREAM_M(8);
-  else STREAM_M(16);
-#undef STREAM_M
+      seed0, seed1, d.thr16, d.inv_keep)
+#define STREAM1(MODE)                                                     \
+  do { if (r <= 8) STREAM(8, MODE, 1); else STREAM(16, MODE, 1); } while (0)
+#define STREAM2(MODE)                                                     \
+  do { if (r <= 8) STREAM(8, MODE, 2); else STREAM(16, MODE, 2); } while (0)
+  if (na == 1) LORA_MODE_SWITCH(d, STREAM1);
+  else if (d.mode == 2) STREAM2(2);        // the dual form takes no mask
+  else STREAM2(0);
+#undef STREAM2
+#undef STREAM1
 #undef STREAM
   if (nsplit > 1)
     launch_reduce_partials(part, out, nsplit, (long)na * M * r, s);
@@ -683,15 +711,13 @@ void launch_lora_contract(const void* X, const void* W, const void* Mk,
   long gw = DTX_CDIV(M, 128);
   dim3 grid((int)(gw < 128 ? (gw < 1 ? 1 : gw) : 128), nsplit);
   float* dst = nsplit > 1 ? part : out;
-  unsigned thr16 = 0; float ik = 1.f;
-  if (!Mk && keep < 1.f) dropout_spec(keep, &thr16, &ik);
+  const LoraDropout d(Mk, keep);
 #define CONTRACT(MODE)                                                    \
   lora_contract_kernel<MODE><<<grid, DTX_BLOCK, 0, s>>>(                  \
       (const unsigned short*)X, (const unsigned short*)W,                 \
-      (const unsigned short*)Mk, dst, M, K, r, kspan, seed, thr16, ik)
-  if (Mk) CONTRACT(1);
-  else if (keep < 1.f) CONTRACT(2);
-  else CONTRACT(0);
+      (const unsigned short*)Mk, dst, M, K, r, kspan, seed, d.thr16,      \
+      d.inv_keep)
+  LORA_MODE_SWITCH(d, CONTRACT);
 #undef CONTRACT
   if (nsplit > 1)
     launch_reduce_partials(part, out, nsplit, M * r, s);
@@ -701,10 +727,8 @@ void launch_lora_expand_add(void* Y, const float* T, const void* WT,
                             const void* Mk, long M, int N, int r,
                             float scale, unsigned long long seed,
                             float keep, hipStream_t s) {
-  const bool rng = !Mk && keep < 1.f;
-  unsigned thr16 = 0; float ik = 1.f;
-  if (rng) dropout_spec(keep, &thr16, &ik);
-  if (r <= 16 && N % 8 == 0 && M >= 64) {
+  if (lora_expand_rng_ok(M, N, r)) {
+    const LoraDropout d(Mk, keep);
     const int gx = DTX_CDIV(N, 2048);
     int rowsplit = 1024 / gx;
     if (rowsplit > M) rowsplit = (int)M;
@@ -714,22 +738,20 @@ void launch_lora_expand_add(void* Y, const float* T, const void* WT,
     lora_expand_add_kernel2<RC, MODE><<<grid, DTX_BLOCK, 0, s>>>(         \
         (unsigned short*)Y, T, (const unsigned short*)WT,                 \
         (const unsigned short*)Mk, M, N, r, scale, rowsplit, seed,        \
-        thr16, ik)
-#define EX2M(RC)                                                          \
+        d.thr16, d.inv_keep)
+#define EX2R(MODE)                                                        \
     do {                                                                  \
-      if (Mk) EX2(RC, 1);                                                 \
-      else if (rng) EX2(RC, 2);                                           \
-      else EX2(RC, 0);                                                    \
+      if (r <= 4) EX2(4, MODE);                                           \
+      else if (r <= 8) EX2(8, MODE);                                      \
+      else EX2(16, MODE);                                                 \
     } while (0)
-    if (r <= 4) EX2M(4);
-    else if (r <= 8) EX2M(8);
-    else EX2M(16);
-#undef EX2M
+    LORA_MODE_SWITCH(d, EX2R);
+#undef EX2R
 #undef EX2
     return;
   }
-  // v1 fallback (r > 16 or tiny M) has no RNG mode: callers materialize
-  // the mask for those shapes (ops dispatch enforces this)
+  // v1 fallback (r > 16 or tiny M) has no RNG mode: the binding refuses
+  // it and ops.lora_expand_add_t materializes the mask for those shapes
   long gw = DTX_CDIV(M, 4);
   int grid = (int)(gw < 2048 ? (gw < 1 ? 1 : gw) : 2048);
   if (Mk) {
@@ -761,25 +783,21 @@ void launch_lora_wgrad(const float* T, const void* X, const void* Mk,
                        hipStream_t st) {
   const int splitm = lora_wgrad_splitm(K, r, M);
   dim3 grid(DTX_CDIV(K, 2048), splitm);
-  const bool rng = !Mk && keep < 1.f;
-  unsigned thr16 = 0; float ik = 1.f;
-  if (rng) dropout_spec(keep, &thr16, &ik);
+  const LoraDropout d(Mk, keep);
   for (int j0 = 0; j0 < r; j0 += 16) {
     int rch = r - j0;
 #define WG(RC, MODE)                                                      \
     lora_wgrad_kernel<RC, MODE><<<grid, DTX_BLOCK, 0, st>>>(              \
         T, (const unsigned short*)X, (const unsigned short*)Mk, part,     \
-        M, K, r, j0, splitm, s, seed, thr16, ik)
-#define CASE(RC)                                                          \
+        M, K, r, j0, splitm, s, seed, d.thr16, d.inv_keep)
+#define WGR(MODE)                                                         \
     do {                                                                  \
-      if (Mk) WG(RC, 1);                                                  \
-      else if (rng) WG(RC, 2);                                            \
-      else WG(RC, 0);                                                     \
+      if (rch <= 4) WG(4, MODE);                                          \
+      else if (rch <= 8) WG(8, MODE);                                     \
+      else WG(16, MODE);                                                  \
     } while (0)
-    if (rch <= 4) CASE(4);
-    else if (rch <= 8) CASE(8);
-    else CASE(16);
-#undef CASE
+    LORA_MODE_SWITCH(d, WGR);
+#undef WGR
 #undef WG
   }
   launch_reduce_partials(part, out, splitm, (long)r * K, st);
@@ -793,9 +811,8 @@ void launch_lora_expand_add_dual(void* Y, const float* T0, const float* T1,
                                  unsigned long long seed0,
                                  unsigned long long seed1, float keep,
                                  hipStream_t s) {
-  const bool rng = keep < 1.f;
-  unsigned thr16 = 0; float ik = 1.f;
-  if (rng) dropout_spec(keep, &thr16, &ik);
+  const LoraDropout d(nullptr, keep);
+  const bool rng = d.mode == 2;
   const int cw = r <= 8 ? 8 : 4;
   const int gx = DTX_CDIV(N, DTX_BLOCK * cw);
   int rowsplit = 1024 / gx;
@@ -806,7 +823,7 @@ void launch_lora_expand_add_dual(void* Y, const float* T0, const float* T1,
   lora_expand_add_dual_kernel<RC, CW, MODE><<<grid, DTX_BLOCK, 0, s>>>(   \
       (unsigned short*)Y, T0, T1, (const unsigned short*)A0,              \
       (const unsigned short*)A1, M, N, r, scale, rowsplit, seed0, seed1,  \
-      thr16, ik)
+      d.thr16, d.inv_keep)
   if (r <= 4) { if (rng) EXD(4, 8, 2); else EXD(4, 8, 0); }
   else if (r <= 8) { if (rng) EXD(8, 8, 2); else EXD(8, 8, 0); }
   else { if (rng) EXD(16, 4, 2); else EXD(16, 4, 0); }

@@ -1,6 +1,7 @@
 """GPU tests for the streaming LoRA path: the r <= 16 contract kernel on
-every plan the dispatch can return, and the dual (two adapters, one
-pass) contract / expand-add ops that QKVProj uses.
+every plan the dispatch can return, the dual (two adapters, one pass)
+contract / expand-add ops that QKVProj uses, and the single-adapter
+LoRALinear node on every dropout mode the op layer can resolve.
 
 Conventions and the 2e-2 bound are those of tests/test_ops_gpu.py; the
 references are ops/reference.py on the CPU. Where the issue promises
@@ -91,7 +92,9 @@ def test_dual_contract_bitwise(M, K, r, keep):
 # lora_wgrad calls and was not kept — profiles/README.md. The wgrad's
 # seed mode shares the RNG counter helper the dual kernels use, so its
 # bits are pinned here against the mask mode and the reference.)
-@pytest.mark.parametrize("M,K,r", [(1024, 4096, 8), (513, 2048, 16)])
+# (130, 264, 64): the r > 16 loop over chunks of 16 ranks, in seed mode
+@pytest.mark.parametrize("M,K,r", [(1024, 4096, 8), (513, 2048, 16),
+                                   (130, 264, 64)])
 def test_wgrad_seed_mode_bits(M, K, r):
     g = gen(M + 3 * K + r)
     x = mk(g, M, K, scale=0.3)
@@ -133,6 +136,84 @@ def test_expand_add_t_matches_expand_add():
     ops.lora_expand_add(y, t, b, 0.5, seed=7, keep=0.9)
     ops.lora_expand_add_t(y2, t, b.t().contiguous(), 0.5, seed=7, keep=0.9)
     assert torch.equal(y, y2)
+
+
+# Seed mode on either side of every boundary of lora_expand_rng_ok: below
+# 64 rows and above rank 16 the kernel has no RNG mode and the op
+# materializes the mask, so both must give the bits of mask mode.
+@pytest.mark.parametrize("M,r", [(63, 8), (64, 8), (100, 32)])
+def test_expand_add_t_seed_mode_boundaries(M, r):
+    g = gen(31 * M + r)
+    N, seed, keep = 264, 2468, 0.9
+    y = mk(g, M, N)
+    y2 = y.clone()
+    t = torch.randn(M, r, generator=g).to(DEV)
+    wt = mk(g, r, N, scale=0.3)
+    assert ops._EXT.lora_expand_rng_ok(M, N, r) == (M >= 64 and r <= 16)
+    ops.lora_expand_add_t(y, t, wt, 0.5, seed=seed, keep=keep)
+    ops.lora_expand_add_t(y2, t, wt, 0.5, ops.dropout_mask(M, N, seed, keep,
+                                                           y2))
+    assert torch.equal(y, y2), "expand-add seed mode != mask mode"
+
+
+# --------------------------------------------------- LoRALinear end to end
+def _expand_peft(y, t, w, scale, seed, keep, rng):
+    """ops.lora_expand_add in the PEFT layout (w [N,r]); dropout in mask
+    mode where the expand-add kernel has no RNG mode."""
+    if keep < 1.0 and not rng:
+        mask = ops.dropout_mask(y.shape[0], y.shape[1], seed, keep, y)
+        return ops.lora_expand_add(y, t, w, scale, mask)
+    return ops.lora_expand_add(y, t, w, scale, None, seed, keep)
+
+
+# kernel2 with and without RNG; under 64 rows (v1 kernel, mask
+# materialized); r > 16 (32x32 contract, chunked wgrad, v1 kernel)
+@pytest.mark.parametrize("M,r,keep", [(200, 8, 1.0), (200, 8, 0.9),
+                                      (48, 8, 0.9), (100, 32, 0.9)])
+def test_lora_linear_node_matches_composed_ops(M, r, keep):
+    from datatunerx_amd.ops.autograd import LoRALinear
+    g = gen(5 * M + r)
+    K, N, scale, seed = 256, 264, 2.0, 13579
+    x = mk(g, 2, M // 2, K).requires_grad_(True)
+    w = mk(g, N, K, scale=0.06)
+    a = mk(g, r, K, scale=0.1).requires_grad_(True)
+    b = mk(g, N, r, scale=0.1).requires_grad_(True)       # non-zero B
+    dy = mk(g, M, N)
+    rng = M >= 64 and r <= 16
+    assert ops._EXT.lora_expand_rng_ok(M, K, r) == rng
+
+    y = LoRALinear.apply(x, w, a, b, scale, None, seed, keep)
+    y.backward(dy.view_as(y))
+
+    with torch.no_grad():
+        x2, a_, b_ = x.detach().reshape(M, K), a.detach(), b.detach()
+        y_c = torch.nn.functional.linear(x2, w)
+        t = ops.lora_contract(x2, a_, None, seed, keep)
+        _expand_peft(y_c, t, b_, scale, 0, 1.0, rng)
+        dx = dy @ w
+        dt = ops.lora_contract(dy, b_.t().contiguous())
+        db = ops.lora_wgrad(t, dy, scale).t().contiguous()
+        da = ops.lora_wgrad(dt, x2, scale, None, seed, keep)
+        _expand_peft(dx, dt, a_.t().contiguous(), scale, seed, keep, rng)
+
+    assert torch.equal(y.reshape(M, N), y_c), "y"
+    assert torch.equal(x.grad.reshape(M, K), dx), "dx"
+    assert torch.equal(a.grad, da.to(a.dtype)), "dA"
+    assert torch.equal(b.grad, db.to(b.dtype)), "dB"
+
+
+def test_lora_linear_node_single_row_is_gemv():
+    from datatunerx_amd.ops.autograd import lora_linear
+    g = gen(77)
+    K, N, r, scale = 256, 264, 8, 2.0
+    x = mk(g, 1, 1, K)
+    w = mk(g, N, K, scale=0.06)
+    a, b = mk(g, r, K, scale=0.1), mk(g, N, r, scale=0.1)
+    y = lora_linear(x, w, a, b, scale)
+    y_c = ops.gemv(x.reshape(1, K), w)
+    ops.lora_expand_add(y_c, ops.lora_contract(x.reshape(1, K), a), b, scale)
+    assert y.shape == (1, 1, N)
+    assert torch.equal(y.reshape(1, N), y_c)
 
 
 # ------------------------------------------------------ QKVProj end to end

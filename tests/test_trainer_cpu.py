@@ -4,6 +4,7 @@ adapter layout, resume restores optimizer state (BASELINE configs[0])."""
 import json
 import os
 
+import pytest
 import torch
 
 from datatunerx_amd.data.dataset import SFTDataset
@@ -247,6 +248,53 @@ def test_rng_dropout_cpu_consistency():
     t_seed = ref.lora_contract(x, a, seed=seed, keep=keep)
     t_mask = ref.lora_contract(x, a, mask=m1.to(x.dtype))
     assert torch.equal(t_seed, t_mask)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("r", [8, 32])
+def test_lora_module_dropout_equals_composed_reference(r, dtype):
+    """A bare LoRALinearModule training with dropout, 20 rows, below and
+    above rank 16: one seed drawn from torch's generator, and output and
+    gradients equal, bit for bit, the reference ops composed by hand in
+    mask mode with ref.dropout_mask of that seed."""
+    from datatunerx_amd.models.lora import LoRALinearModule
+    from datatunerx_amd.ops import reference as ref
+    K, N, rows, p = 64, 72, 20, 0.1
+    torch.manual_seed(1234)
+    mod = LoRALinearModule(K, N, r=r, alpha=16.0, dropout=p, dtype=dtype)
+    with torch.no_grad():
+        mod.weight.copy_(torch.randn(N, K) * 0.1)
+        mod.lora_B.copy_(torch.randn(N, r) * 0.1)       # non-zero B
+    x = torch.randn(4, 5, K).to(dtype).requires_grad_(True)
+    dy = torch.randn(4, 5, N).to(dtype)
+    mod.train()
+    torch.manual_seed(99)
+    y = mod(x)
+    after_forward = torch.get_rng_state()
+    y.backward(dy)
+
+    torch.manual_seed(99)
+    seed = int(torch.randint(0, 2**31 - 1, (1,)).item())
+    assert torch.equal(torch.get_rng_state(), after_forward), \
+        "one draw per call"
+    with torch.no_grad():
+        w, a, b, s = mod.weight, mod.lora_A, mod.lora_B, mod.scale
+        x2, dy2 = x.detach().reshape(rows, K), dy.reshape(rows, N)
+        mask = ref.dropout_mask(rows, K, seed, 1.0 - p, dtype=dtype)
+        bt = b.t().contiguous()
+        y_c = torch.nn.functional.linear(x2, w)
+        t = ref.lora_contract(x2, a, mask)
+        ref.lora_expand_add_t(y_c, t, bt, s)
+        dx = dy2 @ w
+        dt = ref.lora_contract(dy2, bt)
+        db = ref.lora_wgrad(t, dy2, s).t().contiguous().to(dtype)
+        da = ref.lora_wgrad(dt, x2, s, mask).to(dtype)
+        ref.lora_expand_add_t(dx, dt, a, s, mask)
+    assert (mask == 0).any() and (mask > 1).any()
+    assert torch.equal(y.reshape(rows, N), y_c)
+    assert torch.equal(x.grad.reshape(rows, K), dx)
+    assert torch.equal(mod.lora_A.grad, da)
+    assert torch.equal(mod.lora_B.grad, db)
 
 
 def test_residual_epilogue_fold_matches_separate_add():
