@@ -13,6 +13,8 @@ torn down after scoring.
 
 from __future__ import annotations
 
+import copy
+import json
 import math
 import os
 from typing import List, Optional
@@ -29,154 +31,141 @@ class KVCache:
     """BSHD cache ([B, max_s, Hkv, D]) matching the attention kernels'
     native layout — appends along dim 1.
 
-    update() returns (k, v, len_dev): len_dev is None on the eager path
-    (the returned tensors are length-exact prefixes) and a device int32
-    scalar in graph mode (full-capacity tensors whose live length the
-    decode kernel reads on device — hipGraph-replayable)."""
+    update() returns (k, v, len_dev) in one of two modes. Host mode (no
+    counters, or S > 1): append at the host counter `cur`; the returned
+    tensors are the length-exact prefix and len_dev is None. Device mode
+    (counters given and S == 1): one token per row written at wpos[b];
+    the returned tensors are full-capacity and len_dev is len32, the
+    per-row live length the decode kernel reads on device — no host
+    value enters the step, so it replays from a hipGraph. wpos (int64
+    [B], an index into the cache flattened to [B * max_s] slots) and
+    len32 (int32 [B]) belong to a _DecodeState and are shared by every
+    layer's cache."""
 
     def __init__(self, B, Hkv, max_s, D, device, dtype,
-                 graph_pos=None, graph_len=None):
+                 wpos=None, len32=None):
         self.k = torch.zeros(B, max_s, Hkv, D, device=device, dtype=dtype)
         self.v = torch.zeros(B, max_s, Hkv, D, device=device, dtype=dtype)
         self.cur = 0
-        self.graph_pos = graph_pos       # int64 [1]: write index
-        self.graph_len = graph_len       # int32 [1]: length incl. new tok
+        self.wpos, self.len32 = wpos, len32
+
+    def row_view(self, i):
+        """Host-mode B = 1 cache over row i's storage: ragged rows
+        prefill one at a time through it."""
+        row = copy.copy(self)
+        row.k, row.v = self.k[i:i + 1], self.v[i:i + 1]
+        row.cur, row.wpos, row.len32 = 0, None, None
+        return row
 
     def update(self, k, v):
         S = k.shape[1]
-        if self.graph_pos is not None and S == 1 and k.is_cuda:
-            # graph-safe: device-indexed write, device-read length
-            self.k.index_copy_(1, self.graph_pos, k)
-            self.v.index_copy_(1, self.graph_pos, v)
-            return self.k, self.v, self.graph_len
-        self.k[:, self.cur:self.cur + S] = k
-        self.v[:, self.cur:self.cur + S] = v
-        self.cur += S
-        kk, vv = self.k[:, :self.cur], self.v[:, :self.cur]
-        if self.k.shape[0] > 1 or not k.is_cuda:
-            # batch>1 / CPU paths want contiguous; the GPU decode kernel
-            # takes the dense prefix view directly (no per-token copy)
-            kk, vv = kk.contiguous(), vv.contiguous()
-        return kk, vv, None
+        if self.wpos is not None and S == 1:
+            # one flat index_copy_ for every B: an advanced-index put at
+            # (row, pos) costs single-stream decode 2 % (64 writes a
+            # token at 7B; profiles/README.md, serving decode)
+            self.k.view(-1, *k.shape[2:]).index_copy_(0, self.wpos, k[:, 0])
+            self.v.view(-1, *v.shape[2:]).index_copy_(0, self.wpos, v[:, 0])
+            return self.k, self.v, self.len32
+        # a right-padded batched prefill lands here too: per-row len32
+        # bounds every later read and decode overwrites the first pad
+        # slot, so pad K/V beyond a row's real length is never consumed
+        # (pads sit AFTER real tokens: no real query attends one)
+        start, self.cur = self.cur, self.cur + S
+        self.k[:, start:self.cur] = k
+        self.v[:, start:self.cur] = v
+        if self.k.shape[0] == 1 and k.is_cuda:
+            # the GPU decode kernel takes the dense prefix view directly
+            # (no per-token copy)
+            return self.k[:, :self.cur], self.v[:, :self.cur], None
+        if start == 0:
+            return k, v, None            # the prefix IS what came in
+        # batch>1 / CPU paths want contiguous
+        return (self.k[:, :self.cur].contiguous(),
+                self.v[:, :self.cur].contiguous(), None)
 
 
-class _BatchedGraphedDecoder:
-    """hipGraph-captured BATCHED decode step (fixed batch MAXB, padded
-    rows): one replay per token for the whole batch, greedy argmax
-    in-graph, per-row position/length counters device-resident. Built
-    once per engine (under the capture lock) and reused; requests pad
-    to MAXB with dummy rows."""
+class _DecodeState:
+    """Counters and layer caches of one ragged decode batch. Row b's
+    next token is written at index pos[b] (pos32 feeds rope, wpos ==
+    b * max_s + pos is the flat cache slot) and attends len32[b] keys;
+    every method keeps len32 == pos + 1, so a device-mode update never
+    attends an empty row. Batched decode shares one weight stream across
+    the batch — single-stream decode is WEIGHT-bandwidth-bound, so this
+    is the scaling axis for serving throughput."""
+
+    def __init__(self, B, Hkv, max_s, D, layers, device, dtype):
+        self.B, self.max_s = B, max_s
+        self._row0 = torch.arange(B, device=device) * max_s
+        self.wpos = self._row0.clone()
+        self.pos32 = torch.zeros(B, dtype=torch.int32, device=device)
+        self.len32 = torch.ones(B, dtype=torch.int32, device=device)
+        self.caches = [KVCache(B, Hkv, max_s, D, device, dtype,
+                               wpos=self.wpos, len32=self.len32)
+                       for _ in range(layers)]
+
+    def set_state(self, lens):
+        """After prefill: row b holds lens[b] tokens."""
+        pos = torch.tensor(lens, dtype=torch.long,
+                           device=self.wpos.device)
+        self.wpos.copy_(self._row0 + pos)
+        self.pos32.copy_(pos)
+        self.len32.copy_(pos + 1)
+
+    def reset(self):
+        """Empty rows. No cache zeroing needed: prefill overwrites rows
+        up to their length and attention never reads past len32."""
+        self.set_state([0] * self.B)
+        for c in self.caches:
+            c.cur = 0
+
+    def advance(self):
+        self.wpos += 1
+        self.pos32 += 1
+        self.len32 += 1
+
+
+class _GraphedDecoder(_DecodeState):
+    """hipGraph-captured decode step (torch.cuda.CUDAGraph) at fixed
+    batch B and cache capacity max_s: the whole token forward replays
+    as one graph — positions, cache lengths and the adapter of each row
+    are device tensors the captured kernels read at replay, so ONE graph
+    serves every sequence length and adapter assignment. Built once per
+    engine (under the capture lock) and reset per request; a batch pads
+    to B with dummy rows. The graph's static outputs are `logits`
+    [B, 1, V] and `out` [B], its greedy argmax."""
 
     def __init__(self, model, cfg, device, B, max_s):
-        self.B, self.max_s = B, max_s
-        dtype = next(model.parameters()).dtype
-        self.pos64 = torch.zeros(B, dtype=torch.long, device=device)
-        self.pos32 = torch.zeros(B, dtype=torch.int32, device=device)
-        self.len32 = torch.zeros(B, dtype=torch.int32, device=device)
-        self.caches = [
-            BatchedKVCache(B, cfg.num_key_value_heads, max_s,
-                           cfg.head_dim, device, dtype,
-                           pos64=self.pos64, len32=self.len32)
-            for _ in range(cfg.num_hidden_layers)]
+        super().__init__(B, cfg.num_key_value_heads, max_s, cfg.head_dim,
+                         cfg.num_hidden_layers, device,
+                         next(model.parameters()).dtype)
         self.input = torch.ones(B, 1, dtype=torch.long, device=device)
-        self.model = model
-        # multi-adapter models: the adapter of each row lives in a
-        # device buffer the captured kernels read at replay, so ONE
-        # graph serves every assignment (-1 = base / dummy row)
+        # -1 = base model / dummy row
         self.adapter_idx, akw = _graph_adapter_buffer(model, B, device)
-        with torch.no_grad():
-            for _ in range(3):
-                lg = model(self.input, pos_dev=self.pos32,
+
+        def forward():
+            logits = model(self.input, pos_dev=self.pos32,
                            kv_caches=self.caches, **akw)
-                lg[:, -1].argmax(-1)
+            return logits, logits[:, -1].argmax(-1)
+
+        with torch.no_grad():
+            for _ in range(3):          # warmup: allocator + kernels
+                forward()
             torch.cuda.synchronize()
             self.graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.graph):
-                lg = model(self.input, pos_dev=self.pos32,
-                           kv_caches=self.caches, **akw)
-                self.out = lg[:, -1].argmax(-1)
-
-    def reset(self):
-        self.pos64.zero_()
-        self.pos32.zero_()
-        self.len32.zero_()
+                self.logits, self.out = forward()
 
     def set_adapters(self, idx):
         """idx: one adapter index per row of the padded batch."""
         if self.adapter_idx is not None:
             self.adapter_idx.copy_(torch.tensor(idx, dtype=torch.int32))
 
-    def set_state(self, lens):
-        pos = torch.tensor(lens, dtype=torch.long,
-                           device=self.pos64.device)
-        self.pos64.copy_(pos)
-        self.pos32.copy_(pos.to(torch.int32))
-        self.len32.copy_((pos + 1).to(torch.int32))
-
     def step(self, cur):
-        """cur: [B,1] int64 device. Returns next tokens [B] (device)."""
-        self.input.copy_(cur)
+        """cur: this step's input tokens — [B, 1] int64 on device, or a
+        host int when B == 1. Refreshes `logits` and `out`."""
+        self.input[:] = cur
         self.graph.replay()
-        self.pos64 += 1
-        self.pos32 += 1
-        self.len32 += 1
-        return self.out
-
-
-class BatchedKVCache:
-    """Ragged batched decode cache: rows prefill individually (row_view
-    writes through a dim-0 slice), then decode appends ONE token per row
-    at per-row positions (pos64 [B] int64) and attends per-row lengths
-    (len32 [B] int32 — the decode kernel / CPU ref read them per b).
-    Batched decode shares one weight stream across the batch — the
-    single-stream decode is WEIGHT-bandwidth-bound, so this is the
-    scaling axis for serving throughput."""
-
-    def __init__(self, B, Hkv, max_s, D, device, dtype,
-                 pos64=None, len32=None):
-        self.k = torch.zeros(B, max_s, Hkv, D, device=device, dtype=dtype)
-        self.v = torch.zeros(B, max_s, Hkv, D, device=device, dtype=dtype)
-        # pos/len may be SHARED across layers (the graphed decoder
-        # advances one set of counters for all layer caches)
-        self.pos64 = (pos64 if pos64 is not None else
-                      torch.zeros(B, dtype=torch.long, device=device))
-        self.len32 = (len32 if len32 is not None else
-                      torch.zeros(B, dtype=torch.int32, device=device))
-        self._rows = torch.arange(B, device=device)
-
-    class _RowView:
-        def __init__(self, parent, i):
-            self.parent, self.i = parent, i
-            self.cur = 0
-
-        def update(self, k, v):
-            S = k.shape[1]
-            self.parent.k[self.i, self.cur:self.cur + S] = k[0]
-            self.parent.v[self.i, self.cur:self.cur + S] = v[0]
-            self.cur += S
-            return (self.parent.k[self.i:self.i + 1, :self.cur],
-                    self.parent.v[self.i:self.i + 1, :self.cur], None)
-
-    def row_view(self, i):
-        return BatchedKVCache._RowView(self, i)
-
-    def update(self, k, v):
-        if k.shape[1] > 1:
-            # batched RIGHT-PADDED prefill: write all rows up to the
-            # padded length; per-row len32 (set by the caller) bounds
-            # every later read, and decode overwrites the first pad
-            # slot, so pad K/V beyond a row's real length is never
-            # consumed. Returns len_dev=None: prefill attention runs
-            # plain causal over the padded batch (pads sit AFTER real
-            # tokens, so no real query attends one).
-            S = k.shape[1]
-            self.k[:, :S] = k
-            self.v[:, :S] = v
-            return k, v, None
-        # batched decode append: k/v [B, 1, Hkv, D] at per-row positions
-        self.k[self._rows, self.pos64] = k[:, 0]
-        self.v[self._rows, self.pos64] = v[:, 0]
-        return self.k, self.v, self.len32
+        self.advance()
 
 
 def builtin_config(name: str, **lora_kw):
@@ -242,8 +231,6 @@ def build_model(name: str, device, adapter_dir: Optional[str] = None,
     lora_kw = dict(lora_kw or {})
     if adapter_dir and not lora_kw:
         # adapt the LoRA geometry to the checkpoint's adapter_config.json
-        import json
-        import os
         cfg_path = os.path.join(adapter_dir, "adapter_config.json")
         if os.path.exists(cfg_path):
             with open(cfg_path) as f:
@@ -255,22 +242,20 @@ def build_model(name: str, device, adapter_dir: Optional[str] = None,
     from ..models.hf_io import (is_hf_model_dir, load_hf_config,
                                 load_hf_weights)
     hf_dir = is_hf_model_dir(name)
+    if hf_dir:
+        family, cfg = "llama", load_hf_config(name, **lora_kw)
+        lora = bool(adapter_dir)
+    else:
+        family, cfg = builtin_config(name, **lora_kw)
+        lora = adapters is None     # a named stack replaces LoRA modules
+    if adapters is not None and family != "llama":
+        raise ValueError(
+            f"multi-adapter serving supports llama models, not {name!r}")
     with torch.device(device):
-        if hf_dir:
-            model = LlamaForCausalLM(load_hf_config(name, **lora_kw),
-                                     lora=bool(adapter_dir), dtype=dtype)
+        if family == "llama":
+            model = LlamaForCausalLM(cfg, lora=lora, dtype=dtype)
         else:
-            family, cfg = builtin_config(name, **lora_kw)
-            if adapters is not None and family != "llama":
-                raise ValueError(
-                    f"multi-adapter serving supports llama models, not "
-                    f"{name!r}")
-            if family == "llama" and adapters is not None:
-                model = LlamaForCausalLM(cfg, lora=False, dtype=dtype)
-            elif family == "llama":
-                model = LlamaForCausalLM(cfg, dtype=dtype)
-            else:
-                model = GPT2ForCausalLM(cfg, dtype=dtype)
+            model = GPT2ForCausalLM(cfg, dtype=dtype)
     if hf_dir:
         load_hf_weights(model, name)   # real local weights
     else:
@@ -291,75 +276,15 @@ def build_model(name: str, device, adapter_dir: Optional[str] = None,
     return model
 
 
-class _GraphedDecoder:
-    """hipGraph-captured decode step (torch.cuda.CUDAGraph): the whole
-    32-layer token forward replays as one graph — position, cache length
-    and the KV write index live in device tensors so the replay needs no
-    re-capture as the sequence grows. Built once per engine at fixed
-    cache capacity; counters reset per request."""
-
-    def __init__(self, model, cfg, device, max_s):
-        self.model, self.max_s = model, max_s
-        dtype = next(model.parameters()).dtype
-        self.pos64 = torch.zeros(1, dtype=torch.long, device=device)
-        self.pos32 = torch.zeros(1, dtype=torch.int32, device=device)
-        self.len32 = torch.ones(1, dtype=torch.int32, device=device)
-        self.caches = [
-            KVCache(1, cfg.num_key_value_heads, max_s, cfg.head_dim,
-                    device, dtype, graph_pos=self.pos64,
-                    graph_len=self.len32)
-            for _ in range(cfg.num_hidden_layers)]
-        self.input_id = torch.zeros(1, 1, dtype=torch.long, device=device)
-        self.adapter_idx, akw = _graph_adapter_buffer(model, 1, device)
-        # warmup (allocator + kernels), then capture
-        with torch.no_grad():
-            for _ in range(3):
-                self.model(self.input_id, pos_dev=self.pos32,
-                           kv_caches=self.caches, **akw)
-            torch.cuda.synchronize()
-            self.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph):
-                self.logits = self.model(self.input_id,
-                                         pos_dev=self.pos32,
-                                         kv_caches=self.caches, **akw)
-
-    def reset(self):
-        self.pos64.zero_()
-        self.pos32.zero_()
-        self.len32.fill_(1)
-        for c in self.caches:
-            c.cur = 0
-
-    def set_adapter(self, g: int):
-        if self.adapter_idx is not None:
-            self.adapter_idx.copy_(torch.tensor([g], dtype=torch.int32))
-
-    def after_prefill(self, n: int):
-        """counters for the first graphed token (written at index n)."""
-        self.pos64.fill_(n)
-        self.pos32.fill_(n)
-        self.len32.fill_(n + 1)
-        for c in self.caches:
-            c.cur = n
-
-    def step(self, token: int):
-        self.input_id[0, 0] = token
-        self.graph.replay()
-        self.pos64 += 1
-        self.pos32 += 1
-        self.len32 += 1
-        return self.logits
-
-
 class InferenceEngine:
-    MAX_BATCH = int(os.environ.get("DTX_SERVE_MAX_BATCH", "8"))
-
     """One generation context over a (shared, read-only) model. For
     concurrent serving, build several engines over the SAME model
     (serve/server.py EnginePool): each holds its own KV caches, hip
     graph and HIP stream, so batch-1 decodes overlap on the GPU instead
     of queueing on one engine lock (decode is latency-bound, not
     occupancy-bound)."""
+
+    MAX_BATCH = int(os.environ.get("DTX_SERVE_MAX_BATCH", "8"))
 
     def __init__(self, model, tokenizer=None, template: str = "llama2",
                  device=None, graph_decode: bool = True,
@@ -438,17 +363,32 @@ class InferenceEngine:
     # distinct graphs on distinct streams are concurrency-safe.
     _capture_lock = __import__("threading").Lock()
 
+    def _capture(self, B, max_s):
+        """A new graphed decoder, or None when its capture fails (the
+        caller decides what that turns off)."""
+        try:
+            with InferenceEngine._capture_lock, self._stream_ctx():
+                return _GraphedDecoder(self.model, self.model.cfg,
+                                       self.device, B, max_s)
+        except Exception:
+            return None
+
     def _get_graphed(self):
+        """Single-stream decoder at full context; a failed capture turns
+        graph decode off for the engine."""
         if self._graphed is None and self._graph_ok:
-            try:
-                with InferenceEngine._capture_lock, self._stream_ctx():
-                    cfg = self.model.cfg
-                    self._graphed = _GraphedDecoder(
-                        self.model, cfg, self.device,
-                        cfg.max_position_embeddings)
-            except Exception:
-                self._graph_ok = False
+            self._graphed = self._capture(
+                1, self.model.cfg.max_position_embeddings)
+            self._graph_ok = self._graphed is not None
         return self._graphed
+
+    def _get_batched_graphed(self, max_s):
+        """MAX_BATCH-row decoder; a failed capture turns off only the
+        batched graph (`_bgraphed` False: not tried again)."""
+        if self._bgraphed is None and self._graph_ok:
+            self._bgraphed = self._capture(InferenceEngine.MAX_BATCH,
+                                           max_s) or False
+        return self._bgraphed or None
 
     def warmup(self):
         """Build the graphed decoder + run one tiny generation NOW (a
@@ -461,6 +401,36 @@ class InferenceEngine:
             torch.cuda.synchronize()
 
     # ------------------------------------------------------------ chat
+    def _encode_messages(self, messages: List[dict]) -> List[int]:
+        """[{role, content}] -> prompt ids through the engine's template:
+        the last system message, completed user/assistant turns as
+        history, the last unanswered user message as the query."""
+        system, history, pending = "", [], None
+        for m in messages:
+            if m["role"] == "system":
+                system = m["content"]
+            elif m["role"] == "user":
+                pending = m["content"]
+            elif m["role"] == "assistant" and pending is not None:
+                history.append((pending, m["content"]))
+                pending = None
+        src, _ = get_template(self.template).encode_oneturn(
+            self.tok, pending or "", "", history, system)
+        return src
+
+    def _delta(self, ids, sent: str, final: bool = False):
+        """(new text, all text sent) for a stream that decoded `ids` and
+        already sent `sent`. Until final, trailing U+FFFD is held back:
+        a multi-byte UTF-8 char split across tokens decodes as a
+        replacement char until the rest arrives; emitting it early would
+        make the concatenated stream differ from the one-shot decode."""
+        text = self.tok.decode(ids)
+        if not final:
+            text = text.rstrip("\ufffd")
+        if len(text) <= len(sent):
+            return "", sent
+        return text[len(sent):], text
+
     def chat(self, messages: List[dict], max_tokens: int = 64,
              temperature: float = 0.0, top_p: float = 1.0,
              adapter: Optional[str] = None) -> str:
@@ -468,75 +438,30 @@ class InferenceEngine:
         of an attached adapter (None: the base model)."""
         self._adapter_index(adapter)
         with self._stream_ctx():
-            return self._chat(messages, max_tokens, temperature, top_p,
-                              adapter)
-
-    def _chat(self, messages: List[dict], max_tokens: int = 64,
-              temperature: float = 0.0, top_p: float = 1.0,
-              adapter: Optional[str] = None) -> str:
-        system = ""
-        history = []
-        query = ""
-        pending_user = None
-        for m in messages:
-            if m["role"] == "system":
-                system = m["content"]
-            elif m["role"] == "user":
-                pending_user = m["content"]
-            elif m["role"] == "assistant" and pending_user is not None:
-                history.append((pending_user, m["content"]))
-                pending_user = None
-        query = pending_user or ""
-        t = get_template(self.template)
-        src, _ = t.encode_oneturn(self.tok, query, "", history, system)
-        ids = self.generate(src, max_tokens, temperature, top_p,
-                            adapter=adapter)
-        return self.tok.decode(ids)
+            ids = self.generate(self._encode_messages(messages),
+                                max_tokens, temperature, top_p,
+                                adapter=adapter)
+            return self.tok.decode(ids)
 
     def chat_stream(self, messages: List[dict], max_tokens: int = 64,
                     temperature: float = 0.0, top_p: float = 1.0,
                     adapter: Optional[str] = None):
-        self._adapter_index(adapter)
-        for delta in self._chat_stream_inner(messages, max_tokens,
-                                             temperature, top_p, adapter):
-            yield delta
-
-    def _chat_stream_inner(self, messages, max_tokens, temperature,
-                           top_p, adapter=None):
         """Like chat() but yields text DELTAS as tokens decode (the
         serving endpoint streams these as SSE chunks). Token-identical
         to chat(): same generate loop, so TP followers running chat()
         stay in collective lockstep with a streaming front rank."""
-        system, history, pending_user = "", [], None
-        for m in messages:
-            if m["role"] == "system":
-                system = m["content"]
-            elif m["role"] == "user":
-                pending_user = m["content"]
-            elif m["role"] == "assistant" and pending_user is not None:
-                history.append((pending_user, m["content"]))
-                pending_user = None
-        t = get_template(self.template)
-        src, _ = t.encode_oneturn(self.tok, pending_user or "", "",
-                                  history, system)
+        self._adapter_index(adapter)
         ids, sent = [], ""
-        for tok_id in self.generate_stream(src, max_tokens, temperature,
-                                           top_p, adapter=adapter):
+        for tok_id in self.generate_stream(
+                self._encode_messages(messages), max_tokens, temperature,
+                top_p, adapter=adapter):
             ids.append(tok_id)
-            full = self.tok.decode(ids)
-            # hold back trailing U+FFFD: a multi-byte UTF-8 char split
-            # across tokens decodes as a replacement char until the
-            # rest arrives; emitting it early would make the
-            # concatenated stream differ from chat() (ADVICE r1).
-            stable = full
-            while stable.endswith("�"):
-                stable = stable[:-1]
-            if len(stable) > len(sent):
-                delta, sent = stable[len(sent):], stable
+            delta, sent = self._delta(ids, sent)
+            if delta:
                 yield delta
-        full = self.tok.decode(ids)
-        if len(full) > len(sent):
-            yield full[len(sent):]      # flush any held-back tail
+        delta, sent = self._delta(ids, sent, final=True)
+        if delta:
+            yield delta
 
     @torch.no_grad()
     def generate(self, prompt_ids: List[int], max_new_tokens: int = 64,
@@ -577,9 +502,9 @@ class InferenceEngine:
             # hipGraph-replayed decode: prefill eagerly into the graph's
             # caches, then one graph replay per token
             gd.reset()
-            gd.set_adapter(gi)
+            gd.set_adapters([gi])
             logits = self.model(ids, pos0=0, kv_caches=gd.caches, **akw)
-            gd.after_prefill(len(prompt_ids))
+            gd.set_state([len(prompt_ids)])
             nxt = self._sample(logits[0, -1], temperature, top_p)
             for _ in range(max_new_tokens):
                 if self._is_stop(nxt):
@@ -588,8 +513,10 @@ class InferenceEngine:
                 n_out += 1
                 if len(prompt_ids) + n_out + 1 >= gd.max_s:
                     break
-                logits = gd.step(nxt)
-                nxt = self._sample(logits[0, -1], temperature, top_p)
+                gd.step(nxt)
+                # sampled from the logits, not gd.out: one tie-breaking
+                # rule for graphed and eager decode
+                nxt = self._sample(gd.logits[0, -1], temperature, top_p)
             return
         if self.is_llama:
             cfg = self.model.cfg
@@ -680,17 +607,6 @@ class InferenceEngine:
             raise ValueError(f"{len(adapters)} adapters for {n} prompts")
         return [self._adapter_index(a) for a in adapters]
 
-    def _get_batched_graphed(self, max_s):
-        if self._bgraphed is None and self._graph_ok:
-            try:
-                with InferenceEngine._capture_lock, self._stream_ctx():
-                    self._bgraphed = _BatchedGraphedDecoder(
-                        self.model, self.model.cfg, self.device,
-                        InferenceEngine.MAX_BATCH, max_s)
-            except Exception:
-                self._bgraphed = False
-        return self._bgraphed or None
-
     @torch.no_grad()
     def _generate_batch(self, prompts, max_new_tokens, temperature,
                         top_p, budgets=None, adapters=None):
@@ -702,6 +618,90 @@ class InferenceEngine:
                 outs[i].append(t)
         return outs
 
+    def _batch_state(self, n, lmax, max_new_tokens, greedy):
+        """Decode state for n prompts of at most lmax tokens: the
+        graphed MAX_BATCH-row decoder when the batch fits it (greedy, on
+        GPU), else eager state of exactly n rows."""
+        cfg = self.model.cfg
+        if greedy and self.device.type == "cuda" and \
+                n <= InferenceEngine.MAX_BATCH:
+            cap = min(cfg.max_position_embeddings,
+                      int(os.environ.get("DTX_SERVE_MAXS", "2048")))
+            gd = self._get_batched_graphed(cap) \
+                if lmax + max_new_tokens + 8 < cap else None
+            if gd is not None:
+                gd.reset()
+                return gd
+        max_s = min(cfg.max_position_embeddings,
+                    lmax + max_new_tokens + 8)
+        return _DecodeState(n, cfg.num_key_value_heads, max_s,
+                            cfg.head_dim, cfg.num_hidden_layers,
+                            self.device,
+                            next(self.model.parameters()).dtype)
+
+    def _batch_prefill(self, st, prompts, aidx, temperature, top_p):
+        """Prefill every row into st's caches and hand the row lengths
+        over to its counters. Returns each row's first sampled token."""
+        B, lens = len(prompts), [len(p) for p in prompts]
+        nxt = [0] * B
+        if B > 1 and self.device.type == "cuda":
+            # ONE right-padded batched prefill (pads never attended:
+            # causal + pads-after-real; len32 bounds decode reads)
+            padded = torch.zeros(B, max(lens), dtype=torch.long,
+                                 device=self.device)
+            for i, ids in enumerate(prompts):
+                padded[i, :len(ids)] = torch.tensor(ids,
+                                                    dtype=torch.long)
+            logits = self.model(padded, pos0=0, kv_caches=st.caches,
+                                **self._selection(aidx))
+            for i in range(B):
+                nxt[i] = self._sample(logits[i, lens[i] - 1],
+                                      temperature, top_p)
+        else:
+            for i, ids in enumerate(prompts):
+                row = [c.row_view(i) for c in st.caches]
+                t = torch.tensor([ids], dtype=torch.long,
+                                 device=self.device)
+                logits = self.model(t, pos0=0, kv_caches=row,
+                                    **self._selection([aidx[i]]))
+                nxt[i] = self._sample(logits[0, -1], temperature, top_p)
+        st.set_state(lens)
+        return nxt
+
+    def _batch_step(self, st, cur, akw, temperature, top_p):
+        """One token for every row from the [B, 1] input `cur`: (tokens
+        on the host, the next step's input)."""
+        if isinstance(st, _GraphedDecoder):
+            st.step(cur)
+            return st.out.tolist(), st.out.view(-1, 1)
+        logits = self.model(cur, kv_caches=st.caches, pos_dev=st.pos32,
+                            **akw)
+        st.advance()
+        if temperature and temperature > 0:
+            toks = [self._sample(logits[i, -1], temperature, top_p)
+                    for i in range(st.B)]
+        else:
+            toks = logits[:, -1].argmax(-1).tolist()
+        return toks, torch.tensor(toks, dtype=torch.long,
+                                  device=self.device).view(-1, 1)
+
+    def _emit(self, toks, done, count, budgets):
+        """One step's [(row, token)] emissions. A row is done at a stop
+        token or at its budget; dummy rows (beyond budgets) never emit."""
+        emitted = []
+        for i, t in enumerate(toks):
+            if done[i]:
+                continue
+            if self._is_stop(t):
+                done[i] = True
+            elif i < len(budgets):
+                if count[i] < budgets[i]:
+                    emitted.append((i, t))
+                    count[i] += 1
+                if count[i] >= budgets[i]:
+                    done[i] = True
+        return emitted
+
     @torch.no_grad()
     def _generate_batch_steps(self, prompts, max_new_tokens, temperature,
                               top_p, budgets=None, adapters=None):
@@ -711,141 +711,38 @@ class InferenceEngine:
         per-row adapter names."""
         assert self.is_llama, "batched decode is the Llama path"
         aidx = self._adapter_indices(adapters, len(prompts))
-        cfg = self.model.cfg
-        greedy = not (temperature and temperature > 0)
-        lens0 = [len(p) for p in prompts]
-        if not prompts or min(lens0) == 0:
-            raise ValueError("empty prompt in batch")
-        gd = None
-        if greedy and self.device.type == "cuda" and \
-                len(prompts) <= InferenceEngine.MAX_BATCH:
-            cap = min(cfg.max_position_embeddings,
-                      int(os.environ.get("DTX_SERVE_MAXS", "2048")))
-            if max(lens0) + max_new_tokens + 8 < cap:
-                gd = self._get_batched_graphed(cap)
-        if gd is not None:
-            # pad the batch to the graph's fixed MAXB with dummy rows
-            prompts = list(prompts) + \
-                [[self.tok.bos_token_id]] * (gd.B - len(prompts))
-        B = len(prompts)
-        aidx = aidx + [-1] * (B - len(aidx))     # dummy rows: base
-        akw = self._selection(aidx)
         lens = [len(p) for p in prompts]
-        max_s = gd.max_s if gd is not None else min(
-            cfg.max_position_embeddings,
-            max(lens) + max_new_tokens + 8)
-        dtype = next(self.model.parameters()).dtype
-        if gd is not None:
-            # no cache zeroing needed: prefill overwrites rows up to
-            # len and attention never reads past len32
-            gd.reset()
-            gd.set_adapters(aidx)
-            caches = gd.caches
-        else:
-            caches = [BatchedKVCache(B, cfg.num_key_value_heads, max_s,
-                                     cfg.head_dim, self.device, dtype)
-                      for _ in range(cfg.num_hidden_layers)]
-        nxt = [0] * B
-        lmax = max(lens)
-        if B > 1 and self.device.type == "cuda":
-            # ONE right-padded batched prefill (pads never attended:
-            # causal + pads-after-real; len32 bounds decode reads)
-            padded = torch.zeros(B, lmax, dtype=torch.long,
-                                 device=self.device)
-            for i, ids in enumerate(prompts):
-                padded[i, :len(ids)] = torch.tensor(ids,
-                                                    dtype=torch.long)
-            logits = self.model(padded, pos0=0, kv_caches=caches, **akw)
-            for i in range(B):
-                nxt[i] = self._sample(logits[i, lens[i] - 1],
-                                      temperature, top_p)
-        else:
-            for i, ids in enumerate(prompts):
-                row = [c.row_view(i) for c in caches]
-                t = torch.tensor([ids], dtype=torch.long,
-                                 device=self.device)
-                logits = self.model(t, pos0=0, kv_caches=row,
-                                    **self._selection([aidx[i]]))
-                nxt[i] = self._sample(logits[0, -1], temperature, top_p)
-        pos = torch.tensor(lens, dtype=torch.long, device=self.device)
-        if gd is not None:
-            gd.set_state(lens)
-            pos32 = gd.pos32
-        else:
-            for c in caches:
-                c.pos64.copy_(pos)
-                c.len32.copy_((pos + 1).to(torch.int32))
-            pos32 = pos.to(torch.int32)
-        n_live = len(lens0)
+        if not prompts or min(lens) == 0:
+            raise ValueError("empty prompt in batch")
+        n_live = len(prompts)
+        st = self._batch_state(
+            n_live, max(lens), max_new_tokens,
+            greedy=not (temperature and temperature > 0))
+        # a graphed decoder has a fixed batch: pad with dummy rows on
+        # the base model
+        prompts = list(prompts) + \
+            [[self.tok.bos_token_id]] * (st.B - n_live)
+        aidx = aidx + [-1] * (st.B - n_live)
+        if isinstance(st, _GraphedDecoder):
+            st.set_adapters(aidx)
         if budgets is None:
             budgets = [max_new_tokens] * n_live
-        count = [0] * n_live
-        done = [False] * B
-        first = []
-        for i in range(B):
-            if self._is_stop(nxt[i]):
-                done[i] = True
-            elif i < n_live:
-                if count[i] < budgets[i]:
-                    first.append((i, nxt[i]))
-                    count[i] += 1
-                if count[i] >= budgets[i]:
-                    done[i] = True
-        yield first
+        count, done = [0] * n_live, [False] * st.B
+        nxt = self._batch_prefill(st, prompts, aidx, temperature, top_p)
+        yield self._emit(nxt, done, count, budgets)
         cur = torch.tensor(nxt, dtype=torch.long,
-                           device=self.device).view(B, 1)
-        p32 = pos32
-        cap = max_s - max(lens) - 2
+                           device=self.device).view(-1, 1)
+        akw = self._selection(aidx)
+        cap = st.max_s - max(lens) - 2
         for _ in range(min(max_new_tokens - 1, cap)):
             if all(done[:n_live]):
                 break
-            if gd is not None:
-                out = gd.step(cur)
-                toks = out.tolist()
-                cur = out.view(B, 1)
-            else:
-                logits = self.model(cur, kv_caches=caches, pos_dev=p32,
-                                    **akw)
-                for c in caches:
-                    c.pos64 += 1
-                    c.len32 += 1
-                p32 += 1
-                if temperature and temperature > 0:
-                    toks = [self._sample(logits[i, -1], temperature,
-                                         top_p) for i in range(B)]
-                else:
-                    toks = logits[:, -1].argmax(-1).tolist()
-                cur = torch.tensor(toks, dtype=torch.long,
-                                   device=self.device).view(B, 1)
-            emitted = []
-            for i, t in enumerate(toks):
-                if done[i]:
-                    continue
-                if self._is_stop(t):
-                    done[i] = True
-                elif i < n_live:
-                    emitted.append((i, t))
-                    count[i] += 1
-                    if count[i] >= budgets[i]:
-                        done[i] = True
-            yield emitted
+            toks, cur = self._batch_step(st, cur, akw, temperature, top_p)
+            yield self._emit(toks, done, count, budgets)
 
     def _encode_requests(self, requests):
-        t = get_template(self.template)
-        prompts = []
-        for r in requests:
-            system, history, pending = "", [], None
-            for m in r.get("messages", []):
-                if m["role"] == "system":
-                    system = m["content"]
-                elif m["role"] == "user":
-                    pending = m["content"]
-                elif m["role"] == "assistant" and pending is not None:
-                    history.append((pending, m["content"]))
-                    pending = None
-            src, _ = t.encode_oneturn(self.tok, pending or "", "",
-                                      history, system)
-            prompts.append(src)
+        prompts = [self._encode_messages(r.get("messages", []))
+                   for r in requests]
         budgets = [int(r.get("max_tokens", 64)) for r in requests]
         temp = float(requests[0].get("temperature", 0.0))
         top_p = float(requests[0].get("top_p", 1.0))
@@ -889,30 +786,20 @@ class InferenceEngine:
         n = len(requests)
         ids = [[] for _ in range(n)]
         sent = [""] * n
-        live = [True] * n
         with self._stream_ctx():
             for emitted in self._generate_batch_steps(
                     prompts, max(budgets), temp, top_p, budgets=budgets,
                     adapters=names):
-                step_rows = set()
-                for i, t in emitted:
+                for i, t in emitted:      # at most one token per row
                     ids[i].append(t)
-                    step_rows.add(i)
-                for i in step_rows:
-                    full = self.tok.decode(ids[i])
-                    stable = full
-                    while stable.endswith("\ufffd"):
-                        stable = stable[:-1]
-                    if len(stable) > len(sent[i]):
-                        delta = stable[len(sent[i]):]
-                        sent[i] = stable
+                    delta, sent[i] = self._delta(ids[i], sent[i])
+                    if delta:
                         yield i, delta
         for i in range(n):
-            if live[i]:
-                full = self.tok.decode(ids[i])
-                if len(full) > len(sent[i]):
-                    yield i, full[len(sent[i]):]
-                yield i, None
+            delta, sent[i] = self._delta(ids[i], sent[i], final=True)
+            if delta:
+                yield i, delta
+            yield i, None
 
     # ----------------------------------------------------------- score
     @torch.no_grad()

@@ -506,6 +506,77 @@ def test_generate_batch_matches_sequential():
     assert batched == seq
 
 
+def test_kv_cache_modes_agree():
+    """One counter-backed cache (right-padded prefill, then device-mode
+    single-token updates at per-row positions) holds, row by row, exactly
+    what B = 1 host-mode caches hold, and attention over it with the
+    per-row lengths gives exactly the per-row result."""
+    import torch
+
+    from datatunerx_amd.ops.autograd import attention
+    from datatunerx_amd.serve.engine import KVCache, _DecodeState
+    B, Hq, Hkv, D, max_s, lens = 3, 4, 2, 64, 16, [1, 5, 3]
+    cpu = torch.device("cpu")
+    g = torch.Generator().manual_seed(0)
+
+    def rand(*shape):
+        return torch.randn(*shape, generator=g)
+
+    st = _DecodeState(B, Hkv, max_s, D, 1, cpu, torch.float32)
+    cache = st.caches[0]
+    kp, vp = rand(B, max(lens), Hkv, D), rand(B, max(lens), Hkv, D)
+    assert cache.update(kp, vp)[2] is None       # pads hold random k/v
+    st.set_state(lens)
+    hosts = [KVCache(1, Hkv, max_s, D, cpu, torch.float32)
+             for _ in range(B)]
+    for b, h in enumerate(hosts):
+        h.update(kp[b:b + 1, :lens[b]], vp[b:b + 1, :lens[b]])
+    def check_counters():
+        # len == pos + 1; the cache write index is pos in row b's slots
+        assert torch.equal(st.len32, st.pos32 + 1)
+        assert torch.equal(st.wpos, torch.arange(B) * max_s + st.pos32)
+
+    for step in range(1, 4):
+        check_counters()
+        q, k1, v1 = rand(B, 1, Hq, D), rand(B, 1, Hkv, D), \
+            rand(B, 1, Hkv, D)
+        k, v, len_dev = cache.update(k1, v1)
+        assert len_dev is st.len32
+        assert len_dev.tolist() == [n + step for n in lens]
+        o = attention(q, k, v, len_dev=len_dev)
+        for b, h in enumerate(hosts):
+            hk, hv, none = h.update(k1[b:b + 1], v1[b:b + 1])
+            assert none is None and hk.shape[1] == lens[b] + step
+            assert torch.equal(k[b:b + 1, :hk.shape[1]], hk)
+            assert torch.equal(v[b:b + 1, :hv.shape[1]], hv)
+            assert torch.equal(o[b:b + 1], attention(q[b:b + 1], hk, hv))
+        st.advance()
+    check_counters()
+
+
+def test_one_token_batch_and_stream_terminators():
+    """A batch whose prompts are all ONE token long (its prefill is a
+    single-token update of an empty cache) matches per-request
+    generation; every row of a batched stream ends with exactly one
+    (row, None), after that row's last delta."""
+    import torch
+
+    from datatunerx_amd.serve.engine import InferenceEngine, build_model
+    model = build_model("llama-tiny", torch.device("cpu"))
+    eng = InferenceEngine(model, template="vanilla",
+                          device=torch.device("cpu"))
+    assert eng.generate_batch([[5], [6]], max_new_tokens=4) == \
+        [eng.generate([5], max_new_tokens=4),
+         eng.generate([6], max_new_tokens=4)]
+    reqs = [{"messages": [{"role": "user", "content": c}],
+             "max_tokens": n} for c, n in (("alpha", 3), ("beta", 6))]
+    events = list(eng.chat_batch_stream(reqs))
+    for i in range(len(reqs)):
+        row = [d for r, d in events if r == i]
+        assert row.count(None) == 1 and row[-1] is None, events
+        assert "".join(row[:-1]) == eng.chat_batch(reqs)[i]
+
+
 @pytest.mark.slow
 def test_serve_batched_requests_match_sequential(tmp_path):
     """Concurrent non-streaming requests through the BatchingFront give

@@ -321,6 +321,25 @@ def test_serve_engine_decode_gpu():
     assert streamed == out1
 
 
+@pytest.mark.parametrize("B", [1, 3])
+def test_decode_state_one_token_sequences(B):
+    """The first device-mode update after reset() attends exactly the
+    one key it wrote. With a single key the softmax weight is
+    exp2(0) = 1 and 1/l = 1, so o is v, each kv head repeated over its
+    query group, bit for bit. max_s = 600 makes two split-KV chunks, so
+    the empty chunk's partial is combined too."""
+    from datatunerx_amd.ops.autograd import attention
+    from datatunerx_amd.serve.engine import _DecodeState
+    Hq, Hkv, D, max_s = 4, 2, 64, 600
+    st = _DecodeState(B, Hkv, max_s, D, 1, DEV, torch.bfloat16)
+    st.reset()
+    q, k1, v1 = mk(B, 1, Hq, D), mk(B, 1, Hkv, D), mk(B, 1, Hkv, D)
+    k, v, len_dev = st.caches[0].update(k1, v1)
+    assert k.shape[1] == max_s and len_dev is st.len32
+    o = attention(q, k, v, causal=True, len_dev=len_dev)
+    assert torch.equal(o, v1.repeat_interleave(Hq // Hkv, dim=2))
+
+
 @pytest.mark.parametrize("B,Hq,Hkv,Skv,D", [
     (1, 32, 32, 1024, 128),
     (2, 8, 2, 777, 128),       # GQA + ragged cache
