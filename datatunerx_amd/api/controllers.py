@@ -119,6 +119,8 @@ class FinetuneController:
                 a.extend([flag, str(val)])
         add("--stage", p.get("stage"))        # sft | pt | dpo
         add("--dpo_beta", p.get("dpoBeta"))
+        if p.get("packing"):
+            add("--packing", "true")          # sequence packing (sft | pt)
         add("--lr_scheduler_type", p.get("scheduler"))
         add("--optim", p.get("optimizer"))
         if p.get("int4"):

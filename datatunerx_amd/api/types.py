@@ -150,7 +150,9 @@ class Hyperparameter(ApiObject):
     """spec.parameters: scheduler, optimizer, int4, int8, loRA_R,
     loRA_Alpha, loRA_Dropout, learningRate, epochs, blockSize, batchSize,
     warmupRatio, weightDecay, gradAccSteps, trainerType, PEFT, FP16
-    (finetune_controller.go:483-506)."""
+    (finetune_controller.go:483-506); stage (sft | pt | dpo), dpoBeta,
+    packing (bool: sequence packing of the training set, sft and pt
+    only)."""
     kind = "Hyperparameter"
     api_version = GROUP_CORE
 

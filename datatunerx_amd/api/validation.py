@@ -152,6 +152,12 @@ def validate_(obj: ApiObject) -> None:
             st = params.get("stage")
             _require(st is None or st in ("sft", "pt", "dpo"),
                      "spec.parameters.stage must be sft, pt or dpo", errs)
+            pk = params.get("packing")
+            _require(pk is None or isinstance(pk, bool),
+                     "spec.parameters.packing must be a bool", errs)
+            _require(not (pk is True and st == "dpo"),
+                     "spec.parameters.packing is not supported with "
+                     "stage dpo", errs)
     elif isinstance(obj, Dataset):
         md = _dict(obj.spec.get("datasetMetadata"),
                    "spec.datasetMetadata", errs)

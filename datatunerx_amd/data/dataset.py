@@ -149,12 +149,19 @@ class SFTDataset:
 
     @classmethod
     def from_rows_pt(cls, rows, tokenizer,
-                     cutoff_len: int = DEFAULT_CUTOFF_LEN):
+                     cutoff_len: int = DEFAULT_CUTOFF_LEN,
+                     packing: bool = False):
         """Pretraining (stage=pt, parser.py:112-221 stage field): pack
         raw text into fixed cutoff_len blocks with eos separators and
         train on EVERY position (labels = input_ids, no -100 prompt
         masking). Rows use the same columns as sft; instruction and
-        response are concatenated as plain text."""
+        response are concatenated as plain text.
+
+        packing=True adds the document map of each block (`doc_start`:
+        the token after an eos starts a document, and so does the block's
+        first token) and masks the label of every document's first token,
+        so no token attends across an eos or is trained to predict the
+        start of an unrelated document."""
         eos = ([tokenizer.eos_token_id]
                if getattr(tokenizer, "eos_token_id", None) is not None
                else [])
@@ -175,6 +182,19 @@ class SFTDataset:
             ex.append({"input_ids": blk, "labels": list(blk)})
         if not ex and stream:            # corpus shorter than one block
             ex.append({"input_ids": stream, "labels": list(stream)})
+        if packing and eos:
+            for e in ex:
+                ids, labels, ds, start = e["input_ids"], e["labels"], [], 0
+                for j, t in enumerate(ids):
+                    ds.append(start)
+                    if t == eos[0]:
+                        start = j + 1
+                for j in set(ds):
+                    labels[j] = IGNORE_INDEX
+                e["doc_start"] = ds
+        elif packing:
+            raise ValueError("stage=pt packing needs a tokenizer with an "
+                             "eos token to separate documents")
         return cls(ex)
 
     @classmethod
@@ -209,6 +229,119 @@ def collate(batch, pad_token_id: int = 0, pad_to_multiple_of: int = 4,
     if device is not None:
         ids, labels = ids.to(device), labels.to(device)
     return {"input_ids": ids, "labels": labels}
+
+
+def first_fit(lengths: List[int], capacity: int) -> List[List[int]]:
+    """First-fit bin packing in the given order: item i goes into the
+    lowest-numbered bin that still has room. Returns the item indices of
+    each bin. O(n log n): a max-tree over the bins' free space finds the
+    leftmost bin with room in one descent (unopened bins hold `capacity`,
+    so opening a bin is the same descent)."""
+    n = len(lengths)
+    size = 1
+    while size < max(n, 1):
+        size *= 2
+    free = [capacity] * (2 * size)
+    bins: List[List[int]] = []
+    for i, L in enumerate(lengths):
+        if L > capacity:
+            raise ValueError(f"example {i} has {L} tokens, more than "
+                             f"cutoff_len {capacity}; examples are never "
+                             f"split")
+        node = 1
+        while node < size:
+            node = 2 * node if free[2 * node] >= L else 2 * node + 1
+        b = node - size
+        if b == len(bins):
+            bins.append([])
+        bins[b].append(i)
+        free[node] -= L
+        node //= 2
+        while node:
+            free[node] = max(free[2 * node], free[2 * node + 1])
+            node //= 2
+    return bins
+
+
+@dataclass
+class PackedDataset:
+    """Rows of whole examples packed back to back (sequence packing).
+
+    Each row carries `input_ids`, `labels` and `doc_start`: for every
+    token, the row index of the first token of its document. The model
+    masks attention by document and restarts RoPE at each one, so a
+    packed row computes what its documents compute alone. The label of
+    every document's first token is -100: after the shift it would
+    otherwise train the last token of the previous document to predict
+    it."""
+    rows: List[Dict[str, List[int]]]
+    cutoff_len: int
+
+    def __len__(self):
+        return len(self.rows)
+
+    def __getitem__(self, i):
+        return self.rows[i]
+
+    @classmethod
+    def from_dataset(cls, ds, cutoff_len: int = DEFAULT_CUTOFF_LEN,
+                     seed: int = 0):
+        """First-fit packing of `ds` into rows of at most cutoff_len
+        tokens. Examples are never split, every example lands in exactly
+        one row, and a row keeps its examples in dataset order. The
+        examples are visited in a seeded random order, so the result is
+        a function of (dataset, cutoff_len, seed) alone.
+
+        A dataset whose examples already carry `doc_start` (stage=pt
+        blocks built with packing=True) is taken as packed rows as is."""
+        n = len(ds)
+        if n and all("doc_start" in ds[i] for i in range(n)):
+            return cls([ds[i] for i in range(n)], cutoff_len)
+        g = torch.Generator().manual_seed(seed)
+        order = torch.randperm(n, generator=g).tolist()
+        bins = first_fit([len(ds[i]["input_ids"]) for i in order],
+                         cutoff_len)
+        rows = []
+        for members in bins:
+            ids: List[int] = []
+            labels: List[int] = []
+            doc_start: List[int] = []
+            for i in sorted(order[m] for m in members):
+                ex = ds[i]
+                start = len(ids)
+                ids.extend(ex["input_ids"])
+                labels.extend(ex["labels"])
+                labels[start] = IGNORE_INDEX
+                doc_start.extend([start] * len(ex["input_ids"]))
+            rows.append({"input_ids": ids, "labels": labels,
+                         "doc_start": doc_start})
+        return cls(rows, cutoff_len)
+
+
+def collate_packed(batch, pad_token_id: int = 0,
+                   cutoff_len: int = DEFAULT_CUTOFF_LEN, device=None):
+    """Packed rows -> {input_ids, labels, doc_start}, every row padded to
+    cutoff_len: one static [B, cutoff_len] shape for the whole run, so
+    the tuned GEMM picks apply. The pad tail is one more document with
+    all labels -100."""
+    B = len(batch)
+    ids = torch.full((B, cutoff_len), pad_token_id, dtype=torch.long)
+    labels = torch.full((B, cutoff_len), IGNORE_INDEX, dtype=torch.long)
+    doc_start = torch.empty((B, cutoff_len), dtype=torch.int32)
+    for i, b in enumerate(batch):
+        n = len(b["input_ids"])
+        if n > cutoff_len:
+            raise ValueError(f"packed row of {n} tokens exceeds "
+                             f"cutoff_len {cutoff_len}")
+        ids[i, :n] = torch.as_tensor(b["input_ids"], dtype=torch.long)
+        labels[i, :n] = torch.as_tensor(b["labels"], dtype=torch.long)
+        doc_start[i, :n] = torch.as_tensor(b["doc_start"],
+                                           dtype=torch.int32)
+        doc_start[i, n:] = n
+    if device is not None:
+        ids, labels = ids.to(device), labels.to(device)
+        doc_start = doc_start.to(device)
+    return {"input_ids": ids, "labels": labels, "doc_start": doc_start}
 
 
 class ShardedLoader:

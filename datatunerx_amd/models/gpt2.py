@@ -14,6 +14,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from ..ops import doc_end_from_start
 from ..ops.autograd import attention, cross_entropy
 from .lora import FrozenLinear, LoRALinearModule
 
@@ -77,14 +78,15 @@ class GPT2Block(nn.Module):
         self.mlp_fc = FrozenLinear(h, 4 * h, dtype=dtype)
         self.mlp_proj = FrozenLinear(4 * h, h, dtype=dtype)
 
-    def forward(self, x):
+    def forward(self, x, doc_start=None, doc_end=None):
         B, S, _ = x.shape
         H, D = self.cfg.num_attention_heads, self.cfg.head_dim
         hx = self.ln_1(x)
         q = self.q_proj(hx).view(B, S, H, D)
         k = self.k_proj(hx).view(B, S, H, D)
         v = self.v_proj(hx).view(B, S, H, D)
-        o = attention(q, k, v, causal=True)      # BSHD in/out
+        o = attention(q, k, v, causal=True,      # BSHD in/out
+                      doc_start=doc_start, doc_end=doc_end)
         o = o.reshape(B, S, H * D)
         x = x + self.o_proj(o)
         hx = self.ln_2(x)
@@ -122,12 +124,22 @@ class GPT2ForCausalLM(nn.Module):
                 p.zero_()
         return self
 
-    def forward(self, input_ids, labels=None):
+    def forward(self, input_ids, labels=None, doc_start=None):
+        """doc_start[B,S] int32 (sequence packing): attention is masked by
+        document and the learned position ids restart at each one."""
         B, S = input_ids.shape
         pos = torch.arange(S, device=input_ids.device)
-        x = self.wte(input_ids) + self.wpe(pos).unsqueeze(0)
+        doc_end = None
+        if doc_start is None:
+            x = self.wte(input_ids) + self.wpe(pos).unsqueeze(0)
+        else:
+            if tuple(doc_start.shape) != (B, S):
+                raise ValueError("doc_start must match input_ids [B,S]")
+            doc_start = doc_start.to(torch.int32).contiguous()
+            doc_end = doc_end_from_start(doc_start)
+            x = self.wte(input_ids) + self.wpe(pos - doc_start.long())
         for blk in self.blocks:
-            x = blk(x)
+            x = blk(x, doc_start, doc_end)
         x = self.ln_f(x)
         if labels is None:
             return self.lm_head(x)

@@ -16,7 +16,7 @@ from dataclasses import dataclass
 import torch
 import torch.nn as nn
 
-from ..ops import rope_tables
+from ..ops import doc_end_from_start, rope_tables
 from ..ops.autograd import (PairedFrozenGemm, QKVProj, attention,
                             cross_entropy, rmsnorm, rmsnorm_tap,
                             rope, swiglu)
@@ -168,8 +168,12 @@ class LlamaAttention(nn.Module):
                 qm.dropout == vm.dropout)
 
     def forward(self, x, cos, sin, pos0: int = 0, kv_cache=None,
-                pos_dev=None, residual=None, adapters=None):
+                pos_dev=None, residual=None, adapters=None,
+                doc_start=None, doc_end=None):
         B, S, _ = x.shape
+        if doc_start is not None and kv_cache is not None:
+            raise ValueError("doc_start (sequence packing) is a training "
+                             "input; it cannot be combined with a KV cache")
         cfg = self.cfg
         H, Hkv, D = cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim
         if self._fused_qkv():
@@ -196,12 +200,13 @@ class LlamaAttention(nn.Module):
         if self.q_norm is not None:
             q = rmsnorm(q.contiguous(), self.q_norm, cfg.rms_norm_eps)
             k = rmsnorm(k.contiguous(), self.k_norm, cfg.rms_norm_eps)
-        q = rope(q, cos, sin, pos0, pos_dev)
-        k = rope(k, cos, sin, pos0, pos_dev)
+        q = rope(q, cos, sin, pos0, pos_dev, doc_start)
+        k = rope(k, cos, sin, pos0, pos_dev, doc_start)
         len_dev = None
         if kv_cache is not None:
             k, v, len_dev = kv_cache.update(k, v)   # serving path (BSHD)
-        o = attention(q, k, v, causal=True, len_dev=len_dev)
+        o = attention(q, k, v, causal=True, len_dev=len_dev,
+                      doc_start=doc_start, doc_end=doc_end)
         o = o.reshape(B, S, H * D)
         if residual is not None and isinstance(self.o_proj, FrozenLinear):
             return self.o_proj(o, residual)   # residual in GEMM epilogue
@@ -247,10 +252,17 @@ class LlamaDecoderLayer(nn.Module):
         self.mlp = LlamaMLP(cfg, lora, dtype)
 
     def forward(self, x, cos, sin, pos0: int = 0, kv_cache=None,
-                pos_dev=None, adapters=None):
+                pos_dev=None, adapters=None, doc_start=None, doc_end=None):
         h, res = rmsnorm_tap(x, self.input_layernorm,
                              self.cfg.rms_norm_eps)
-        if adapters is None:
+        if doc_start is not None:
+            if adapters is not None:
+                raise ValueError("doc_start cannot be combined with "
+                                 "per-sequence adapters")
+            x = self.self_attn(h, cos, sin, pos0, kv_cache, pos_dev,
+                               residual=res, doc_start=doc_start,
+                               doc_end=doc_end)
+        elif adapters is None:
             x = self.self_attn(h, cos, sin, pos0, kv_cache, pos_dev,
                                residual=res)
         else:
@@ -307,12 +319,30 @@ class LlamaForCausalLM(nn.Module):
         return self
 
     def hidden_states(self, input_ids, pos0: int = 0, kv_caches=None,
-                      pos_dev=None, adapters=None):
+                      pos_dev=None, adapters=None, doc_start=None):
+        """doc_start[B,S] int32 (sequence packing): the row index of the
+        first token of each token's document. Attention is masked by
+        document and RoPE restarts at each one."""
         x = self.embed_tokens(input_ids)
         cos, sin = self.rope_cos, self.rope_sin
+        doc_end = None
+        if doc_start is not None:
+            if tuple(doc_start.shape) != tuple(input_ids.shape):
+                raise ValueError("doc_start must match input_ids [B,S]")
+            doc_start = doc_start.to(torch.int32).contiguous()
+            # once per forward; every layer's dkdv kernel reads it
+            doc_end = doc_end_from_start(doc_start)
         for i, layer in enumerate(self.layers):
             cache = kv_caches[i] if kv_caches is not None else None
-            if self.cfg.gradient_checkpointing and self.training:
+            if doc_start is not None:
+                if self.cfg.gradient_checkpointing and self.training:
+                    x = torch.utils.checkpoint.checkpoint(
+                        layer, x, cos, sin, pos0, cache, None, None,
+                        doc_start, doc_end, use_reentrant=False)
+                else:
+                    x = layer(x, cos, sin, pos0, cache, pos_dev,
+                              doc_start=doc_start, doc_end=doc_end)
+            elif self.cfg.gradient_checkpointing and self.training:
                 x = torch.utils.checkpoint.checkpoint(
                     layer, x, cos, sin, pos0, cache, use_reentrant=False)
             elif adapters is not None:
@@ -323,13 +353,14 @@ class LlamaForCausalLM(nn.Module):
         return rmsnorm(x, self.norm, self.cfg.rms_norm_eps)
 
     def forward(self, input_ids, labels=None, pos0: int = 0,
-                kv_caches=None, pos_dev=None, adapters=None):
+                kv_caches=None, pos_dev=None, adapters=None,
+                doc_start=None):
         """Returns loss (if labels given, shifted CE with -100 ignore)
         else logits. adapters: per-sequence adapter selection for a
         model with attached adapter stacks (models/multilora.py); None
-        runs the base model."""
+        runs the base model. doc_start: packed rows, see hidden_states."""
         h = self.hidden_states(input_ids, pos0, kv_caches, pos_dev,
-                               adapters)
+                               adapters, doc_start)
         if labels is None:
             return self.lm_head(h)
         if os.environ.get("DTX_FUSED_CE") == "1" and \

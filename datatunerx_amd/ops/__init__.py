@@ -72,9 +72,28 @@ def rmsnorm_bwd(dy, x, w, inv, dres=None):
 rope_tables = ref.rope_tables
 
 
-def rope_fwd(x, cos, sin, pos0: int = 0, pos_dev=None):
+def _check_doc_start(doc_start, *others):
+    """Sequence packing: doc_start excludes the serving-side arguments."""
+    if doc_start is None:
+        return
+    if any(o is not None for o in others):
+        raise ValueError("doc_start cannot be combined with len_dev or "
+                         "pos_dev")
+    if doc_start.dtype != torch.int32:
+        raise ValueError("doc_start must be int32")
+
+
+doc_end_from_start = ref.doc_end_from_start
+
+
+def rope_fwd(x, cos, sin, pos0: int = 0, pos_dev=None, doc_start=None):
+    """doc_start[B,S] (sequence packing): positions restart per document,
+    token s sits at pos0 + s - doc_start[b,s]."""
+    _check_doc_start(doc_start, pos_dev)
     if _gpu(x):
-        return _EXT.rope(x, cos, sin, pos0, False, pos_dev)
+        return _EXT.rope(x, cos, sin, pos0, False, pos_dev, doc_start)
+    if doc_start is not None:
+        return ref.rope_fwd(x, cos, sin, pos0, doc_start)
     if pos_dev is not None and pos_dev.numel() > 1:
         # batched ragged decode: per-row positions
         return torch.cat([ref.rope_fwd(x[i:i + 1], cos, sin,
@@ -85,10 +104,11 @@ def rope_fwd(x, cos, sin, pos0: int = 0, pos_dev=None):
     return ref.rope_fwd(x, cos, sin, pos0)
 
 
-def rope_bwd(dy, cos, sin, pos0: int = 0):
+def rope_bwd(dy, cos, sin, pos0: int = 0, doc_start=None):
+    _check_doc_start(doc_start)
     if _gpu(dy):
-        return _EXT.rope(dy, cos, sin, pos0, True)
-    return ref.rope_bwd(dy, cos, sin, pos0)
+        return _EXT.rope(dy, cos, sin, pos0, True, None, doc_start)
+    return ref.rope_bwd(dy, cos, sin, pos0, doc_start)
 
 
 # ---------------------------------------------------------------- SwiGLU
@@ -136,10 +156,21 @@ def xent_dlogits(logits_c, targets, lse, v0: int,
 
 # --------------------------------------------------------- attention
 def attn_fwd(q, k, v, causal: bool = True, scale: float | None = None,
-             len_dev=None):
-    """BSHD: q [B,S,Hq,D], k/v [B,Skv,Hkv,D] -> (o [B,S,Hq,D], lse)."""
+             len_dev=None, doc_start=None):
+    """BSHD: q [B,S,Hq,D], k/v [B,Skv,Hkv,D] -> (o [B,S,Hq,D], lse).
+
+    doc_start[B,S] int32 (sequence packing): kv row j is visible to q row
+    i iff doc_start[i] <= j <= i. Needs causal, S == Skv, S > 1 and no
+    len_dev."""
     if scale is None:
         scale = 1.0 / (q.shape[-1] ** 0.5)
+    if doc_start is not None:
+        _check_doc_start(doc_start, len_dev)
+        ref.check_docs(doc_start, causal, q.shape[1], k.shape[1])
+        if _gpu(q):
+            return _EXT.attn_fwd(q, k, v.contiguous(), causal, scale,
+                                 doc_start)
+        return ref.attn_fwd(q, k, v, causal, scale, doc_start)
     if _gpu(q):
         if q.shape[1] == 1:
             # serving decode: flash-decoding split-KV path (with S=1
@@ -166,9 +197,21 @@ def attn_fwd(q, k, v, causal: bool = True, scale: float | None = None,
 
 
 def attn_bwd(q, k, v, o, do, lse, causal: bool = True,
-             scale: float | None = None):
+             scale: float | None = None, doc_start=None, doc_end=None):
+    """doc_start / doc_end [B,S] int32 (sequence packing): doc_end is
+    derived from doc_start when the caller has not done so already."""
     if scale is None:
         scale = 1.0 / (q.shape[-1] ** 0.5)
+    if doc_start is not None:
+        _check_doc_start(doc_start)
+        ref.check_docs(doc_start, causal, q.shape[1], k.shape[1])
+        if not _gpu(q):
+            return ref.attn_bwd(q, k, v, o, do, lse, causal, scale,
+                                doc_start)
+        if doc_end is None:
+            doc_end = ref.doc_end_from_start(doc_start)
+        return _EXT.attn_bwd(q, k, v, o, do, lse, causal, scale, doc_start,
+                             doc_end)
     if _gpu(q):
         return _EXT.attn_bwd(q, k, v, o, do, lse, causal, scale)
     return ref.attn_bwd(q, k, v, o, do, lse, causal, scale)

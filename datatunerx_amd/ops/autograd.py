@@ -62,20 +62,22 @@ def rmsnorm_tap(x, w, eps: float = 1e-5):
 
 class Rope(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, cos, sin, pos0, pos_dev):
+    def forward(ctx, x, cos, sin, pos0, pos_dev, doc_start):
         ctx.save_for_backward(cos, sin)
         ctx.pos0 = pos0
-        return rope_fwd(x, cos, sin, pos0, pos_dev)
+        ctx.doc_start = doc_start
+        return rope_fwd(x, cos, sin, pos0, pos_dev, doc_start)
 
     @staticmethod
     def backward(ctx, dy):
         cos, sin = ctx.saved_tensors
-        return (rope_bwd(dy.contiguous(), cos, sin, ctx.pos0),
-                None, None, None, None)
+        return (rope_bwd(dy.contiguous(), cos, sin, ctx.pos0,
+                         ctx.doc_start),
+                None, None, None, None, None)
 
 
-def rope(x, cos, sin, pos0: int = 0, pos_dev=None):
-    return Rope.apply(x, cos, sin, pos0, pos_dev)
+def rope(x, cos, sin, pos0: int = 0, pos_dev=None, doc_start=None):
+    return Rope.apply(x, cos, sin, pos0, pos_dev, doc_start)
 
 
 class SwiGLU(torch.autograd.Function):
@@ -99,31 +101,37 @@ class Attention(torch.autograd.Function):
     """BSHD flash attention (no transpose copies around the kernel)."""
 
     @staticmethod
-    def forward(ctx, q, k, v, causal, scale, len_dev):
+    def forward(ctx, q, k, v, causal, scale, len_dev, doc_start, doc_end):
         q = q.contiguous()
         if not (q.is_cuda and q.shape[1] == 1):
             # decode (S=1) accepts dense KV-cache prefix views; every
             # other path wants contiguous k/v
             k, v = k.contiguous(), v.contiguous()
-        o, lse = attn_fwd(q, k, v, causal, scale, len_dev)
+        o, lse = attn_fwd(q, k, v, causal, scale, len_dev, doc_start)
         ctx.save_for_backward(q, k, v, o, lse)
         ctx.causal, ctx.scale = causal, scale
+        ctx.doc_start, ctx.doc_end = doc_start, doc_end
         return o
 
     @staticmethod
     def backward(ctx, do):
         q, k, v, o, lse = ctx.saved_tensors
         dq, dk, dv = attn_bwd(q, k, v, o, do.contiguous(), lse,
-                              ctx.causal, ctx.scale)
-        return dq, dk, dv, None, None, None
+                              ctx.causal, ctx.scale, ctx.doc_start,
+                              ctx.doc_end)
+        return dq, dk, dv, None, None, None, None, None
 
 
 def attention(q, k, v, causal: bool = True, scale: float | None = None,
-              len_dev=None):
-    """q [B,S,Hq,D], k/v [B,Skv,Hkv,D] -> o [B,S,Hq,D]."""
+              len_dev=None, doc_start=None, doc_end=None):
+    """q [B,S,Hq,D], k/v [B,Skv,Hkv,D] -> o [B,S,Hq,D].
+
+    doc_start / doc_end [B,S] int32: document-masked attention for packed
+    rows (see ops.attn_fwd)."""
     if scale is None:
         scale = 1.0 / (q.shape[-1] ** 0.5)
-    return Attention.apply(q, k, v, causal, scale, len_dev)
+    return Attention.apply(q, k, v, causal, scale, len_dev, doc_start,
+                           doc_end)
 
 
 class CrossEntropy(torch.autograd.Function):

@@ -21,6 +21,14 @@
 //     S^T, dP^T as in the forward (swapped), then
 //     dQ[q][d] += mfma(A=conv(dS^T), B=K^T-rows)
 //
+// DOCS = true (sequence packing, causal, S == Skv): kv row j is visible
+// to q row i iff doc_start[i] <= j <= i, equivalently i < doc_end[j]. The
+// dq kernel masks and skips by doc_start exactly as the forward does; the
+// dkdv kernel, whose lanes own kv columns, uses doc_end. Dead elements get
+// p = 0 exactly, so other documents add exact zeros: no atomics, and the
+// result does not depend on what the other documents hold. DOCS = false
+// compiles to the plain kernels.
+//
 // Numerics contract: ops/reference.py attn_bwd.
 #include "dtx_mfma.h"
 
@@ -43,7 +51,7 @@ struct DkdvLds {
   // (4 blocks/CU co-resident) and the staged global traffic
 };
 
-template <int D>
+template <int D, bool DOCS>
 __global__ __launch_bounds__(512, 1)
 void attn_bwd_dkdv2_kernel(const unsigned short* __restrict__ Q,
                            const unsigned short* __restrict__ Kp,
@@ -53,6 +61,7 @@ void attn_bwd_dkdv2_kernel(const unsigned short* __restrict__ Q,
                            const float* __restrict__ delta_in,
                            unsigned short* __restrict__ dK,
                            unsigned short* __restrict__ dV,
+                           const int* __restrict__ doc_end,  // [B,S] (DOCS)
                            int B, int Hq, int Hkv, int S, int Skv,
                            float scale, int causal) {
   constexpr int DC16 = D / 16;
@@ -109,6 +118,24 @@ void attn_bwd_dkdv2_kernel(const unsigned short* __restrict__ Q,
     }
   }
 
+  // DOCS: de = exclusive end of the document of this lane's kv row, read
+  // once here, ahead of the staged pipeline (clamped index; rows past
+  // Skv are dead by the kvg >= Skv select anyway). doc_end is
+  // non-decreasing, so lane 0 / lane 31 hold the wave's min / max, and
+  // the block's last row bounds the last q stage with a live element.
+  int de = 0, de_lo = 0, de_hi = 0, qs_end = 0;
+  if constexpr (DOCS) {
+    // clamped into (kv, S]: a malformed map must not move a stage index
+    // out of range
+    const int* derow = doc_end + (long)b * S;
+    const int kc = min(kw + l31, S - 1);
+    de = min(max(derow[kc], kc + 1), S);
+    de_lo = __builtin_amdgcn_readlane(de, 0);
+    de_hi = __builtin_amdgcn_readlane(de, 31);
+    const int kl = min(kv0b + 127, S - 1);
+    qs_end = (min(max(derow[kl], kl + 1), S) + 63) / 64;
+  }
+
   f32x16 acc[ND32];                        // dV or dK by role
 #pragma unroll
   for (int c = 0; c < ND32; ++c)
@@ -122,7 +149,7 @@ void attn_bwd_dkdv2_kernel(const unsigned short* __restrict__ Q,
 
     // q rows that can see this block's kv rows: q + diag >= kv0b
     const int qs_lo = causal ? max(0, (kv0b - diag) / 64) : 0;
-    const int qs_hi = (S + 63) / 64;
+    const int qs_hi = DOCS ? qs_end : (S + 63) / 64;
     // T14 async-stage split: stage qs+1's global loads are issued while
     // stage qs computes; the LDS write happens after the barrier. The
     // stage's lse (even waves) / delta (odd waves) ride along in one
@@ -177,8 +204,9 @@ void attn_bwd_dkdv2_kernel(const unsigned short* __restrict__ Q,
       const int q0 = q0s + qh * 32;
       const int qoff = qh * 32;                  // LDS row offset
       // wave skip: its kv rows all above this q-tile's diagonal
-      const bool live_tile =
+      bool live_tile =
           !(q0 >= S || (causal && (q0 + 31 + diag < kw)));
+      if constexpr (DOCS) live_tile = live_tile && (q0 < de_hi);
       if (live_tile) {
 
       // ---- the tile's lse2 / delta in one shot: the C-layout rows
@@ -218,8 +246,9 @@ void attn_bwd_dkdv2_kernel(const unsigned short* __restrict__ Q,
       // ---- P = exp2(s*kscale - lse2); dS = P o (dP - delta) * scale
       // One uniform choice per tile between the unmasked and the masked
       // exp loop. P overwrites sv; dS overwrites dpv.
-      const bool interior = (kv0b + 128 <= Skv) && (q0 + 32 <= S) &&
-                            (!causal || (kw + 31 <= q0 + diag));
+      bool interior = (kv0b + 128 <= Skv) && (q0 + 32 <= S) &&
+                      (!causal || (kw + 31 <= q0 + diag));
+      if constexpr (DOCS) interior = interior && (q0 + 32 <= de_lo);
       if (interior) {
 #pragma unroll
         for (int r = 0; r < 16; ++r)
@@ -229,8 +258,9 @@ void attn_bwd_dkdv2_kernel(const unsigned short* __restrict__ Q,
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int qg = q0 + crow(r, hi);
-          const bool dead = (kvg >= Skv) | (qg >= S) |
-                            (causal && (kvg > qg + diag));
+          bool dead = (kvg >= Skv) | (qg >= S) |
+                      (causal && (kvg > qg + diag));
+          if constexpr (DOCS) dead |= qg >= de;
           sv[r] = dead ? 0.f
                        : __builtin_exp2f(sv[r] * kscale - l4[r >> 2][r & 3]);
         }
@@ -297,7 +327,7 @@ struct DqLds {
   // ds_read_b64_tr_b16 (tr_bfrag) — no transposed KT image
 };
 
-template <int D>
+template <int D, bool DOCS>
 __global__ __launch_bounds__(512, 1)
 void attn_bwd_dq2_kernel(const unsigned short* __restrict__ Q,
                          const unsigned short* __restrict__ Kp,
@@ -307,6 +337,7 @@ void attn_bwd_dq2_kernel(const unsigned short* __restrict__ Q,
                          const float* __restrict__ lse_in,
                          float* __restrict__ delta_out,
                          unsigned short* __restrict__ dQ,
+                         const int* __restrict__ doc_start,  // [B,S] (DOCS)
                          int B, int Hq, int Hkv, int S, int Skv,
                          float scale, int causal) {
   constexpr int KVB = 64;
@@ -387,6 +418,20 @@ void attn_bwd_dq2_kernel(const unsigned short* __restrict__ Q,
   const int kv_hi = causal ? min(Skv - 1, q_hi_blk + diag) : (Skv - 1);
   const int nstages = kv_hi / 128 + 1;     // 128 kv rows per stage
 
+  // DOCS: per-lane first visible kv row, wave min / max, first stage
+  // (as in attn_fwd2_kernel)
+  int ds = 0, ds_lo = 0, ds_hi = 0, st_lo = 0;
+  if constexpr (DOCS) {
+    // clamped into [0, q]: a malformed map must not move a stage or a
+    // tile index out of range
+    const int* dsrow = doc_start + (long)b * S;
+    const int qc = min(qw + l31, S - 1);
+    ds = min(max(dsrow[qc], 0), qc);
+    ds_lo = __builtin_amdgcn_readlane(ds, 0);
+    ds_hi = __builtin_amdgcn_readlane(ds, 31);
+    st_lo = min(max(dsrow[q0], 0), q0) / 128;
+  }
+
   // T14 async-stage split (as in fwd/dkdv)
   constexpr int KIT = (128 * (D / 8)) / 512;
   short8v stg[KIT * 2];
@@ -418,23 +463,25 @@ void attn_bwd_dq2_kernel(const unsigned short* __restrict__ Q,
           stg[it * 2 + 1];
     }
   };
-  issue_stage(0);
+  issue_stage(st_lo);
   write_stage(0);
   __syncthreads();
   int cur = 0;
-  for (int st2 = 0; st2 < nstages; ++st2) {
+  for (int st2 = st_lo; st2 < nstages; ++st2) {
     if (st2 + 1 < nstages) issue_stage(st2 + 1);
     const int kvs = st2 * 128;
 
     for (int kh = 0; kh < 2; ++kh) {
     const int kv0 = kvs + kh * KVB;
     const int koff = kh * KVB;               // LDS row/col offset
-    const bool wave_dead = (kv0 > kv_hi) ||
-                           (causal && (kv0 > qw + 31 + diag));
+    bool wave_dead = (kv0 > kv_hi) ||
+                     (causal && (kv0 > qw + 31 + diag));
+    if constexpr (DOCS) wave_dead = wave_dead || (kv0 + KVB - 1 < ds_lo);
     if (!wave_dead) {
       const int qg = qw + l31;
-      const bool interior = (kv0 + KVB <= Skv) &&
-                            (!causal || (kv0 + KVB - 1 <= qw + diag));
+      bool interior = (kv0 + KVB <= Skv) &&
+                      (!causal || (kv0 + KVB - 1 <= qw + diag));
+      if constexpr (DOCS) interior = interior && (kv0 >= ds_hi);
 #pragma unroll
       for (int ss = 0; ss < 2; ++ss) {
         // S^T and dP^T for kv subtile ss (C-layout: kv rows on regs,
@@ -459,8 +506,9 @@ void attn_bwd_dq2_kernel(const unsigned short* __restrict__ Q,
             p = __builtin_exp2f(st[r] * kscale - lse2);
           } else {
             const int kvg = kv0 + ss * 32 + crow(r, hi);
-            const bool dead = (kvg >= Skv) | (qg >= S) |
-                              (causal && (kvg > qg + diag));
+            bool dead = (kvg >= Skv) | (qg >= S) |
+                        (causal && (kvg > qg + diag));
+            if constexpr (DOCS) dead |= kvg < ds;
             p = dead ? 0.f : __builtin_exp2f(st[r] * kscale - lse2);
           }
           dst[r] = p * (dpt[r] - dlt) * scale;
@@ -507,45 +555,66 @@ void attn_bwd_dq2_kernel(const unsigned short* __restrict__ Q,
 }
 
 // ------------------------------------------------------------- launchers
+// doc_end / doc_start: nullptr = plain kernels (DOCS = false).
+template <int D, bool DOCS>
+static void launch_dkdv_d(const void* q, const void* k, const void* v,
+                          const void* dO, const float* lse,
+                          const float* delta, void* dk, void* dv,
+                          const int* doc_end, int B, int Hq, int Hkv,
+                          int S, int Skv, float scale, int causal,
+                          hipStream_t st) {
+  dim3 grid(DTX_CDIV(Skv, 128), B * Hkv);
+  attn_bwd_dkdv2_kernel<D, DOCS><<<grid, 512, 0, st>>>(
+      (const unsigned short*)q, (const unsigned short*)k,
+      (const unsigned short*)v, (const unsigned short*)dO,
+      lse, delta, (unsigned short*)dk, (unsigned short*)dv, doc_end,
+      B, Hq, Hkv, S, Skv, scale, causal);
+}
+
 void launch_attn_bwd_dkdv(const void* q, const void* k, const void* v,
                           const void* dO, const float* lse,
-                          const float* delta, void* dk, void* dv, int B,
-                          int Hq, int Hkv, int S, int Skv, int D,
-                          float scale, int causal, hipStream_t st) {
-  dim3 grid(DTX_CDIV(Skv, 128), B * Hkv);
+                          const float* delta, void* dk, void* dv,
+                          const int* doc_end, int B, int Hq, int Hkv,
+                          int S, int Skv, int D, float scale, int causal,
+                          hipStream_t st) {
+#define DTX_DKDV(DD, DOCS)                                                 \
+  launch_dkdv_d<DD, DOCS>(q, k, v, dO, lse, delta, dk, dv, doc_end, B, Hq, \
+                          Hkv, S, Skv, scale, causal, st)
   if (D == 128) {
-    attn_bwd_dkdv2_kernel<128><<<grid, 512, 0, st>>>(
-        (const unsigned short*)q, (const unsigned short*)k,
-        (const unsigned short*)v, (const unsigned short*)dO,
-        lse, delta, (unsigned short*)dk, (unsigned short*)dv,
-        B, Hq, Hkv, S, Skv, scale, causal);
+    if (doc_end) DTX_DKDV(128, true); else DTX_DKDV(128, false);
   } else if (D == 64) {
-    attn_bwd_dkdv2_kernel<64><<<grid, 512, 0, st>>>(
-        (const unsigned short*)q, (const unsigned short*)k,
-        (const unsigned short*)v, (const unsigned short*)dO,
-        lse, delta, (unsigned short*)dk, (unsigned short*)dv,
-        B, Hq, Hkv, S, Skv, scale, causal);
+    if (doc_end) DTX_DKDV(64, true); else DTX_DKDV(64, false);
   }
+#undef DTX_DKDV
+}
+
+template <int D, bool DOCS>
+static void launch_dq_d(const void* q, const void* k, const void* v,
+                        const void* dO, const void* o, const float* lse,
+                        float* delta, void* dq, const int* doc_start,
+                        int B, int Hq, int Hkv, int S, int Skv,
+                        float scale, int causal, hipStream_t st) {
+  dim3 grid(DTX_CDIV(S, 256), B * Hq);
+  attn_bwd_dq2_kernel<D, DOCS><<<grid, 512, 0, st>>>(
+      (const unsigned short*)q, (const unsigned short*)k,
+      (const unsigned short*)v, (const unsigned short*)dO,
+      (const unsigned short*)o, lse, delta, (unsigned short*)dq,
+      doc_start, B, Hq, Hkv, S, Skv, scale, causal);
 }
 
 // Also writes delta[B,Hq,S]; launch before launch_attn_bwd_dkdv.
 void launch_attn_bwd_dq(const void* q, const void* k, const void* v,
                         const void* dO, const void* o, const float* lse,
-                        float* delta, void* dq, int B, int Hq,
-                        int Hkv, int S, int Skv, int D, float scale,
-                        int causal, hipStream_t st) {
-  dim3 grid(DTX_CDIV(S, 256), B * Hq);
+                        float* delta, void* dq, const int* doc_start,
+                        int B, int Hq, int Hkv, int S, int Skv, int D,
+                        float scale, int causal, hipStream_t st) {
+#define DTX_DQ(DD, DOCS)                                                   \
+  launch_dq_d<DD, DOCS>(q, k, v, dO, o, lse, delta, dq, doc_start, B, Hq,  \
+                        Hkv, S, Skv, scale, causal, st)
   if (D == 128) {
-    attn_bwd_dq2_kernel<128><<<grid, 512, 0, st>>>(
-        (const unsigned short*)q, (const unsigned short*)k,
-        (const unsigned short*)v, (const unsigned short*)dO,
-        (const unsigned short*)o, lse, delta, (unsigned short*)dq,
-        B, Hq, Hkv, S, Skv, scale, causal);
+    if (doc_start) DTX_DQ(128, true); else DTX_DQ(128, false);
   } else if (D == 64) {
-    attn_bwd_dq2_kernel<64><<<grid, 512, 0, st>>>(
-        (const unsigned short*)q, (const unsigned short*)k,
-        (const unsigned short*)v, (const unsigned short*)dO,
-        (const unsigned short*)o, lse, delta, (unsigned short*)dq,
-        B, Hq, Hkv, S, Skv, scale, causal);
+    if (doc_start) DTX_DQ(64, true); else DTX_DQ(64, false);
   }
+#undef DTX_DQ
 }

@@ -24,6 +24,13 @@
 // domain internally, natural-log lse out). Causal + GQA + ragged S by
 // masking; interior tiles skip the mask; waves fully above the causal
 // diagonal skip compute.
+//
+// DOCS = true (sequence packing): doc_start[B,S] holds, per token, the row
+// index of the first token of its document; kv row j is visible to q row i
+// iff doc_start[i] <= j <= i. The lane owns q column qw+l31 and keeps its
+// doc_start in one register; stages and 64-row tiles that lie wholly before
+// the wave's first document are skipped, boundary tiles add kv < doc_start
+// to the causal select. DOCS = false compiles to the plain causal kernel.
 #include "dtx_mfma.h"
 
 template <int D>
@@ -36,13 +43,14 @@ struct AttnFwdLds {
 
 // 8 waves x 32 q-rows per workgroup. A 4-wave (128-row) workgroup measured
 // 45% slower on the training shape: profiles/README.md, "Attention round 2".
-template <int D>
+template <int D, bool DOCS>
 __global__ __launch_bounds__(512, 1)
 void attn_fwd2_kernel(const unsigned short* __restrict__ Q,
                       const unsigned short* __restrict__ Kp,
                       const unsigned short* __restrict__ Vp,
                       unsigned short* __restrict__ O,
                       float* __restrict__ lse_out,
+                      const int* __restrict__ doc_start,   // [B,S] (DOCS)
                       int B, int Hq, int Hkv, int S, int Skv,
                       float scale, int causal) {
   constexpr int KVB = 64;
@@ -98,6 +106,22 @@ void attn_fwd2_kernel(const unsigned short* __restrict__ Q,
   const int kv_hi = causal ? min(Skv - 1, q_hi_blk + diag) : (Skv - 1);
   const int nstages = kv_hi / 128 + 1;     // 128 kv rows per stage
 
+  // DOCS: ds = first visible kv row of this lane's q row (rows past S
+  // reuse the last row's; they are never stored). doc_start is
+  // non-decreasing, so lane 0 / lane 31 hold the wave's min / max and
+  // the block's first row bounds the first stage that holds a live row.
+  int ds = 0, ds_lo = 0, ds_hi = 0, st_lo = 0;
+  if constexpr (DOCS) {
+    // clamped into [0, q]: a malformed map must not move a stage or a
+    // tile index out of range
+    const int* dsrow = doc_start + (long)b * S;
+    const int qc = min(qw + l31, S - 1);
+    ds = min(max(dsrow[qc], 0), qc);
+    ds_lo = __builtin_amdgcn_readlane(ds, 0);
+    ds_hi = __builtin_amdgcn_readlane(ds, 31);
+    st_lo = min(max(dsrow[q0], 0), q0) / 128;
+  }
+
   // T14 async-stage split: the next stage's K/VT global loads are
   // issued while the current stage computes; LDS writes after the
   // barrier.  KIT/VIT iterations cover the 128-row K and VT tiles.
@@ -131,19 +155,20 @@ void attn_fwd2_kernel(const unsigned short* __restrict__ Q,
           stg[it * 2 + 1];
     }
   };
-  issue_stage(0);
+  issue_stage(st_lo);
   write_stage(0);
   __syncthreads();
   int cur = 0;
-  for (int st2 = 0; st2 < nstages; ++st2) {
+  for (int st2 = st_lo; st2 < nstages; ++st2) {
     if (st2 + 1 < nstages) issue_stage(st2 + 1);
     const int kvs = st2 * 128;
 
     for (int half = 0; half < 2; ++half) {
     const int kv0 = kvs + half * KVB;
     const int koff = half * KVB;             // LDS row offset
-    const bool wave_dead = (kv0 > kv_hi) ||
-                           (causal && (kv0 > qw + 31 + diag));
+    bool wave_dead = (kv0 > kv_hi) ||
+                     (causal && (kv0 > qw + 31 + diag));
+    if constexpr (DOCS) wave_dead = wave_dead || (kv0 + KVB - 1 < ds_lo);
     if (!wave_dead) {
       // ---- S^T tiles: s[ss] = K[kv0+ss*32..][*] x Q^T  (C-layout:
       // row kv = crow(r,hi)+32*ss, col q = qw+l31)
@@ -164,9 +189,10 @@ void attn_fwd2_kernel(const unsigned short* __restrict__ Q,
       // the exp2 later: p = exp2(fma(s, kscale, -m)), saving the
       // separate 32-mult scale pass on every tile — guide "exp2+fma
       // fold")
-      const bool interior =
+      bool interior =
           (kv0 + KVB <= Skv) &&
           (!causal || (kv0 + KVB - 1 <= qw + diag));
+      if constexpr (DOCS) interior = interior && (kv0 >= ds_hi);
       const int qg = qw + l31;
       if (!interior) {
 #pragma unroll
@@ -175,6 +201,10 @@ void attn_fwd2_kernel(const unsigned short* __restrict__ Q,
           const int kv_b = kv_a + 32;
           bool dead_a = (kv_a >= Skv) | (causal && (kv_a > qg + diag));
           bool dead_b = (kv_b >= Skv) | (causal && (kv_b > qg + diag));
+          if constexpr (DOCS) {
+            dead_a |= kv_a < ds;
+            dead_b |= kv_b < ds;
+          }
           if (dead_a) s0v[r] = NEG_INF;
           if (dead_b) s1v[r] = NEG_INF;
         }
@@ -222,7 +252,7 @@ void attn_fwd2_kernel(const unsigned short* __restrict__ Q,
         conv_c_to_frag(ss ? s1v : s0v, pa[2 * ss], pa[2 * ss + 1]);
 
       // ---- rescale O rows by alpha[q-row] (one bpermute per row)
-      if (!defer && (st2 > 0 || half > 0)) {
+      if (!defer && (st2 > st_lo || half > 0)) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const float a_r = __shfl(alpha, crow(r, hi), 64);
@@ -338,27 +368,32 @@ void launch_transpose_sd(const void* x, void* xt, int B, int S, int H,
       (const unsigned short*)x, (unsigned short*)xt, B, S, H, D);
 }
 
-template <int D>
+template <int D, bool DOCS>
 static void launch_attn_fwd_d(const void* q, const void* k, const void* v,
-                              void* o, float* lse, int B, int Hq, int Hkv,
-                              int S, int Skv, float scale, int causal,
-                              hipStream_t st) {
+                              void* o, float* lse, const int* doc_start,
+                              int B, int Hq, int Hkv, int S, int Skv,
+                              float scale, int causal, hipStream_t st) {
   dim3 grid(DTX_CDIV(S, 256), B * Hq);
-  attn_fwd2_kernel<D><<<grid, 512, 0, st>>>(
+  attn_fwd2_kernel<D, DOCS><<<grid, 512, 0, st>>>(
       (const unsigned short*)q, (const unsigned short*)k,
-      (const unsigned short*)v, (unsigned short*)o, lse,
+      (const unsigned short*)v, (unsigned short*)o, lse, doc_start,
       B, Hq, Hkv, S, Skv, scale, causal);
 }
 
+// doc_start: nullptr = plain causal / full attention (DOCS = false).
 void launch_attn_fwd(const void* q, const void* k, const void* v, void* o,
-                     float* lse, int B, int Hq, int Hkv, int S, int Skv,
-                     int D, float scale, int causal, hipStream_t st) {
-  if (D == 128)
-    launch_attn_fwd_d<128>(q, k, v, o, lse, B, Hq, Hkv, S, Skv, scale,
-                           causal, st);
-  else if (D == 64)
-    launch_attn_fwd_d<64>(q, k, v, o, lse, B, Hq, Hkv, S, Skv, scale,
-                          causal, st);
+                     float* lse, const int* doc_start, int B, int Hq,
+                     int Hkv, int S, int Skv, int D, float scale,
+                     int causal, hipStream_t st) {
+#define DTX_FWD(DD, DOCS)                                                  \
+  launch_attn_fwd_d<DD, DOCS>(q, k, v, o, lse, doc_start, B, Hq, Hkv, S,   \
+                              Skv, scale, causal, st)
+  if (D == 128) {
+    if (doc_start) DTX_FWD(128, true); else DTX_FWD(128, false);
+  } else if (D == 64) {
+    if (doc_start) DTX_FWD(64, true); else DTX_FWD(64, false);
+  }
+#undef DTX_FWD
 }
 
 // ------------------------------------------------------- decode (S=1)

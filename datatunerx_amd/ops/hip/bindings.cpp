@@ -12,7 +12,8 @@ void launch_rmsnorm_bwd(const void*, const void*, const void*, const float*,
                         const void*, void*, float*, float*, int, int,
                         hipStream_t);
 void launch_rope(const void*, const float*, const float*, void*, long, int,
-                 int, int, int, int, const int*, int, hipStream_t);
+                 int, int, int, int, const int*, int, const int*,
+                 hipStream_t);
 void launch_swiglu_fwd(const void*, const void*, void*, long, hipStream_t);
 void launch_swiglu_bwd(const void*, const void*, const void*, void*, void*,
                        long, hipStream_t);
@@ -53,7 +54,8 @@ void launch_lora_wgrad(const float*, const void*, const void*, float*,
                        float*, long, int, int, float, unsigned long long,
                        float, hipStream_t);
 void launch_attn_fwd(const void*, const void*, const void*, void*, float*,
-                     int, int, int, int, int, int, float, int, hipStream_t);
+                     const int*, int, int, int, int, int, int, float, int,
+                     hipStream_t);
 void launch_transpose_sd(const void*, void*, int, int, int, int,
                          hipStream_t);
 int attn_decode_nsplit(int Skv);
@@ -74,12 +76,12 @@ void launch_attn_decode(const void*, const void*, const void*,
                         int, int, float, int, hipStream_t);
 void launch_attn_bwd_dkdv(const void*, const void*, const void*,
                           const void*, const float*, const float*,
-                          void*, void*, int, int, int, int, int, int,
-                          float, int, hipStream_t);
+                          void*, void*, const int*, int, int, int, int,
+                          int, int, float, int, hipStream_t);
 void launch_attn_bwd_dq(const void*, const void*, const void*,
                         const void*, const void*, const float*, float*,
-                        void*, int, int, int, int, int, int, float, int,
-                        hipStream_t);
+                        void*, const int*, int, int, int, int, int, int,
+                        float, int, hipStream_t);
 
 namespace {
 
@@ -91,6 +93,26 @@ void check_bf16_contig(const torch::Tensor& t, const char* name) {
   TORCH_CHECK(t.is_cuda(), name, " must be on GPU");
   TORCH_CHECK(t.scalar_type() == torch::kBFloat16, name, " must be bf16");
   TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
+}
+
+// Sequence-packing maps (doc_start / doc_end): int32 [B,S] on the GPU.
+// The kernels index them unchecked, so shape and layout are pinned here.
+const int* doc_map_ptr(const c10::optional<torch::Tensor>& t, long B,
+                       long S, const char* name) {
+  if (!t.has_value()) return nullptr;
+  TORCH_CHECK(t->is_cuda(), name, " must be on GPU");
+  TORCH_CHECK(t->scalar_type() == torch::kInt, name, " must be int32");
+  TORCH_CHECK(t->dim() == 2 && t->size(0) == B && t->size(1) == S, name,
+              " must be [B,S]");
+  TORCH_CHECK(t->is_contiguous(), name, " must be contiguous");
+  return t->data_ptr<int>();
+}
+
+// doc_start needs the training shape: causal self-attention over S > 1.
+void check_docs_shape(bool causal, long S, long Skv) {
+  TORCH_CHECK(causal, "doc_start requires causal=True");
+  TORCH_CHECK(S == Skv, "doc_start requires S == Skv");
+  TORCH_CHECK(S > 1, "doc_start requires S > 1");
 }
 
 // ------------------------------------------------------------- RMSNorm
@@ -136,13 +158,17 @@ std::vector<torch::Tensor> rmsnorm_bwd(torch::Tensor dy, torch::Tensor x,
 // ---------------------------------------------------------------- RoPE
 torch::Tensor rope(torch::Tensor x, torch::Tensor cosb, torch::Tensor sinb,
                    long pos0, bool backward,
-                   c10::optional<torch::Tensor> pos_dev) {
+                   c10::optional<torch::Tensor> pos_dev,
+                   c10::optional<torch::Tensor> doc_start) {
   check_bf16_contig(x, "x");
   TORCH_CHECK(x.dim() == 4, "x must be [B,S,H,D]");
   TORCH_CHECK(cosb.scalar_type() == torch::kFloat && cosb.is_contiguous());
   const int B = (int)x.size(0), S = (int)x.size(1), H = (int)x.size(2),
             D = (int)x.size(3);
   TORCH_CHECK(D % 8 == 0, "D % 8");
+  const int* dsp = doc_map_ptr(doc_start, B, S, "doc_start");
+  TORCH_CHECK(!(dsp && pos_dev.has_value()),
+              "doc_start cannot be combined with pos_dev");
   const int* pd = nullptr;
   int pos_per_b = 0;
   if (pos_dev.has_value()) {
@@ -159,7 +185,7 @@ torch::Tensor rope(torch::Tensor x, torch::Tensor cosb, torch::Tensor sinb,
   auto y = torch::empty_like(x);
   launch_rope(x.data_ptr(), cosb.data_ptr<float>(), sinb.data_ptr<float>(),
               y.data_ptr(), B, S, H, D, (int)pos0, backward ? 1 : 0, pd,
-              pos_per_b, cur_stream());
+              pos_per_b, dsp, cur_stream());
   return y;
 }
 
@@ -402,7 +428,8 @@ torch::Tensor transpose_sd(torch::Tensor x) {
 // q: [B,S,Hq,D]; k, v: [B,Skv,Hkv,D] — all BSHD, v row-major like k.
 std::vector<torch::Tensor> attn_fwd(torch::Tensor q, torch::Tensor k,
                                     torch::Tensor v, bool causal,
-                                    double scale) {
+                                    double scale,
+                                    c10::optional<torch::Tensor> doc_start) {
   check_bf16_contig(q, "q");
   check_bf16_contig(k, "k");
   check_bf16_contig(v, "v");
@@ -413,10 +440,12 @@ std::vector<torch::Tensor> attn_fwd(torch::Tensor q, torch::Tensor k,
               "v must be BSHD like k");
   TORCH_CHECK(D == 64 || D == 128, "D must be 64 or 128");
   TORCH_CHECK(Hq % Hkv == 0, "GQA group");
+  const int* dsp = doc_map_ptr(doc_start, B, S, "doc_start");
+  if (dsp) check_docs_shape(causal, S, Skv);
   auto o = torch::empty_like(q);
   auto lse = torch::empty({B, Hq, S}, q.options().dtype(torch::kFloat));
   launch_attn_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
-                  lse.data_ptr<float>(), B, Hq, Hkv, S, Skv, D,
+                  lse.data_ptr<float>(), dsp, B, Hq, Hkv, S, Skv, D,
                   (float)scale, causal ? 1 : 0, cur_stream());
   return {o, lse};
 }
@@ -667,7 +696,9 @@ std::vector<torch::Tensor> attn_decode(torch::Tensor q, torch::Tensor k,
 std::vector<torch::Tensor> attn_bwd(torch::Tensor q, torch::Tensor k,
                                     torch::Tensor v, torch::Tensor o,
                                     torch::Tensor dO, torch::Tensor lse,
-                                    bool causal, double scale) {
+                                    bool causal, double scale,
+                                    c10::optional<torch::Tensor> doc_start,
+                                    c10::optional<torch::Tensor> doc_end) {
   check_bf16_contig(q, "q");
   check_bf16_contig(k, "k");
   check_bf16_contig(v, "v");
@@ -676,6 +707,11 @@ std::vector<torch::Tensor> attn_bwd(torch::Tensor q, torch::Tensor k,
             D = (int)q.size(3);
   const int Skv = (int)k.size(1), Hkv = (int)k.size(2);
   check_bf16_contig(o, "o");
+  const int* dsp = doc_map_ptr(doc_start, B, S, "doc_start");
+  const int* dep = doc_map_ptr(doc_end, B, S, "doc_end");
+  TORCH_CHECK((dsp == nullptr) == (dep == nullptr),
+              "doc_start and doc_end go together");
+  if (dsp) check_docs_shape(causal, S, Skv);
   auto delta = torch::empty({B, Hq, S}, q.options().dtype(torch::kFloat));
   // dkdv and dq gather their B-fragments from the ROW-major LDS tiles
   // with ds_read_b64_tr_b16 (tr_bfrag) — no pre-transposed Q/K/dO
@@ -688,12 +724,13 @@ std::vector<torch::Tensor> attn_bwd(torch::Tensor q, torch::Tensor k,
   // reads it. There is no separate delta pass.
   launch_attn_bwd_dq(q.data_ptr(), k.data_ptr(), v.data_ptr(),
                      dO_c.data_ptr(), o.data_ptr(), lse.data_ptr<float>(),
-                     delta.data_ptr<float>(), dq.data_ptr(), B, Hq, Hkv, S,
-                     Skv, D, (float)scale, causal ? 1 : 0, cur_stream());
+                     delta.data_ptr<float>(), dq.data_ptr(), dsp, B, Hq,
+                     Hkv, S, Skv, D, (float)scale, causal ? 1 : 0,
+                     cur_stream());
   launch_attn_bwd_dkdv(q.data_ptr(), k.data_ptr(), v.data_ptr(),
                        dO_c.data_ptr(), lse.data_ptr<float>(),
                        delta.data_ptr<float>(), dk.data_ptr(),
-                       dv.data_ptr(), B, Hq, Hkv, S, Skv, D,
+                       dv.data_ptr(), dep, B, Hq, Hkv, S, Skv, D,
                        (float)scale, causal ? 1 : 0, cur_stream());
   return {dq, dk, dv};
 }
@@ -706,7 +743,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("w"), py::arg("inv"), py::arg("dres") = py::none());
   m.def("rope", &rope, py::arg("x"), py::arg("cosb"), py::arg("sinb"),
         py::arg("pos0"), py::arg("backward"),
-        py::arg("pos_dev") = py::none());
+        py::arg("pos_dev") = py::none(),
+        py::arg("doc_start") = py::none());
   m.def("swiglu_fwd", &swiglu_fwd);
   m.def("swiglu_bwd", &swiglu_bwd);
   m.def("xent_fwd", &xent_fwd);
@@ -737,8 +775,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("seed"), py::arg("keep"), py::arg("like"));
   m.def("adamw", &adamw);
   m.def("l2_norm", &l2_norm);
-  m.def("attn_fwd", &attn_fwd);
-  m.def("attn_bwd", &attn_bwd);
+  m.def("attn_fwd", &attn_fwd, py::arg("q"), py::arg("k"), py::arg("v"),
+        py::arg("causal"), py::arg("scale"),
+        py::arg("doc_start") = py::none());
+  m.def("attn_bwd", &attn_bwd, py::arg("q"), py::arg("k"), py::arg("v"),
+        py::arg("o"), py::arg("dO"), py::arg("lse"), py::arg("causal"),
+        py::arg("scale"), py::arg("doc_start") = py::none(),
+        py::arg("doc_end") = py::none());
   m.def("transpose_sd", &transpose_sd);
   m.def("gemv", &gemv);
   m.def("qgemv_int8", &qgemv_int8, py::arg("x"), py::arg("q"),

@@ -177,12 +177,16 @@ void reduce_partials_kernel(const float* __restrict__ part,
 // ----------------------------------------------------------------- RoPE
 // x [B,S,H,D] bf16; cos/sin [Smax, D/2] f32; rotate-half convention.
 // Each thread: 4 (x1,x2) pairs. backward => sin sign flip.
+// DOCS (sequence packing): doc_start[B,S] is the row index of the first
+// token of each token's document; positions restart there.
+template <bool DOCS>
 __global__ __launch_bounds__(DTX_BLOCK)
 void rope_kernel(const unsigned short* __restrict__ x,
                  const float* __restrict__ cosb,
                  const float* __restrict__ sinb,
                  unsigned short* __restrict__ y,
                  const int* __restrict__ pos_dev,  // graph-mode position
+                 const int* __restrict__ doc_start,  // [B,S] (DOCS)
                  long total_quads,  // B*S*H*(D/2/4)
                  int S, int H, int D, int pos0, int backward,
                  int pos_per_b) {
@@ -197,6 +201,9 @@ void rope_kernel(const unsigned short* __restrict__ x,
     int s_pos = (int)((row / H) % S);
     if (pos_dev && pos_per_b)
       s_pos += pos_dev[row / ((long)S * H)];
+    // positions restart at the document's first row (clamped into
+    // [0, s] so a malformed map cannot index outside the tables)
+    if constexpr (DOCS) s_pos -= min(max(doc_start[row / H], 0), s_pos);
     const long base = row * D;
     short4v x1 = *reinterpret_cast<const short4v*>(x + base + q * 4);
     short4v x2 = *reinterpret_cast<const short4v*>(x + base + D / 2 + q * 4);
@@ -323,11 +330,16 @@ void launch_reduce_partials(const float* part, float* out, int P, long L,
 void launch_rope(const void* x, const float* cosb, const float* sinb,
                  void* y, long B, int S, int H, int D, int pos0,
                  int backward, const int* pos_dev, int pos_per_b,
-                 hipStream_t s) {
+                 const int* doc_start, hipStream_t s) {
   long quads = B * S * H * (D / 8);
-  rope_kernel<<<ew_grid(quads), DTX_BLOCK, 0, s>>>(
-      (const unsigned short*)x, cosb, sinb, (unsigned short*)y, pos_dev, quads,
-      S, H, D, pos0, backward, pos_per_b);
+  if (doc_start)
+    rope_kernel<true><<<ew_grid(quads), DTX_BLOCK, 0, s>>>(
+        (const unsigned short*)x, cosb, sinb, (unsigned short*)y, pos_dev,
+        doc_start, quads, S, H, D, pos0, backward, pos_per_b);
+  else
+    rope_kernel<false><<<ew_grid(quads), DTX_BLOCK, 0, s>>>(
+        (const unsigned short*)x, cosb, sinb, (unsigned short*)y, pos_dev,
+        nullptr, quads, S, H, D, pos0, backward, pos_per_b);
 }
 
 void launch_swiglu_fwd(const void* g, const void* u, void* o, long n,

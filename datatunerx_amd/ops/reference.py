@@ -48,27 +48,49 @@ def rope_tables(seq_len: int, head_dim: int, base: float = 10000.0,
     return freqs.cos().to(dtype), freqs.sin().to(dtype)
 
 
+def doc_end_from_start(doc_start: torch.Tensor) -> torch.Tensor:
+    """Sequence packing: doc_start[B,S] (row index of the first token of
+    each token's document) -> doc_end[B,S], the exclusive end of it."""
+    B, S = doc_start.shape
+    idx = torch.arange(S, device=doc_start.device, dtype=doc_start.dtype)
+    # is_last[s]: token s closes its document
+    is_last = torch.ones(B, S, dtype=torch.bool, device=doc_start.device)
+    is_last[:, :-1] = doc_start[:, 1:] != doc_start[:, :-1]
+    # the next closing index at or after s, via a reversed running min
+    end = torch.where(is_last, idx + 1, torch.full_like(doc_start, S))
+    return end.flip(1).cummin(dim=1).values.flip(1).contiguous()
+
+
+def _rope_cs(cos, sin, pos0, S, D, doc_start):
+    """cos/sin broadcastable to [B,S,H,D/2]; positions restart at each
+    document when doc_start[B,S] is given."""
+    if doc_start is None:
+        return (cos[pos0: pos0 + S].float().view(1, S, 1, D // 2),
+                sin[pos0: pos0 + S].float().view(1, S, 1, D // 2))
+    pos = pos0 + torch.arange(S, device=doc_start.device) - doc_start.long()
+    return (cos[pos].float().unsqueeze(2), sin[pos].float().unsqueeze(2))
+
+
 def rope_fwd(x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor,
-             pos0: int = 0):
-    """Llama rotate-half RoPE. x: [B, S, H, D]; cos/sin: [>=pos0+S, D/2]."""
+             pos0: int = 0, doc_start=None):
+    """Llama rotate-half RoPE. x: [B, S, H, D]; cos/sin: [>=pos0+S, D/2].
+    doc_start[B,S]: the position of token s is pos0 + s - doc_start[b,s]."""
     B, S, H, D = x.shape
     xf = x.float()
     x1, x2 = xf[..., : D // 2], xf[..., D // 2:]
-    c = cos[pos0: pos0 + S].float().view(1, S, 1, D // 2)
-    s = sin[pos0: pos0 + S].float().view(1, S, 1, D // 2)
+    c, s = _rope_cs(cos, sin, pos0, S, D, doc_start)
     y1 = x1 * c - x2 * s
     y2 = x2 * c + x1 * s
     return torch.cat([y1, y2], dim=-1).to(x.dtype)
 
 
 def rope_bwd(dy: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor,
-             pos0: int = 0):
+             pos0: int = 0, doc_start=None):
     """Gradient of rope_fwd = rotation by -theta (transpose of rotation)."""
     B, S, H, D = dy.shape
     df = dy.float()
     d1, d2 = df[..., : D // 2], df[..., D // 2:]
-    c = cos[pos0: pos0 + S].float().view(1, S, 1, D // 2)
-    s = sin[pos0: pos0 + S].float().view(1, S, 1, D // 2)
+    c, s = _rope_cs(cos, sin, pos0, S, D, doc_start)
     x1 = d1 * c + d2 * s
     x2 = -d1 * s + d2 * c
     return torch.cat([x1, x2], dim=-1).to(dy.dtype)
@@ -121,27 +143,59 @@ def softmax_xent_bwd(logits: torch.Tensor, targets: torch.Tensor,
 
 
 # -------------------------------------------------------- flash attention
+def check_docs(doc_start, causal: bool, S: int, Skv: int):
+    """doc_start is defined for the training shape only."""
+    if doc_start is None:
+        return
+    if not causal:
+        raise ValueError("doc_start requires causal=True")
+    if S != Skv:
+        raise ValueError("doc_start requires S == Skv")
+    if S <= 1:
+        raise ValueError("doc_start requires S > 1")
+    if tuple(doc_start.shape) != (doc_start.shape[0], S):
+        raise ValueError("doc_start must be [B,S]")
+
+
+def _visible(S: int, Skv: int, causal: bool, doc_start, device):
+    """Boolean mask [B or 1, 1, S, Skv] of visible (q, kv) pairs, or None.
+    With doc_start: kv row j is visible to q row i iff
+    doc_start[i] <= j <= i."""
+    if not causal:
+        return None
+    mask = torch.ones(S, Skv, dtype=torch.bool, device=device).tril(
+        diagonal=Skv - S).view(1, 1, S, Skv)
+    if doc_start is not None:
+        j = torch.arange(Skv, device=device).view(1, 1, 1, Skv)
+        mask = mask & (j >= doc_start.long().view(-1, 1, S, 1))
+    return mask
+
+
 def attn_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
-             causal: bool = True, scale: float | None = None):
+             causal: bool = True, scale: float | None = None,
+             doc_start=None):
     """BSHD public contract: q [B,S,Hq,D], k/v [B,Skv,Hkv,D].
 
     Returns (o [B,S,Hq,D], lse [f32, B,Hq,S])."""
+    check_docs(doc_start, causal, q.shape[1], k.shape[1])
     o, lse = _attn_fwd_bhsd(q.permute(0, 2, 1, 3), k.permute(0, 2, 1, 3),
-                            v.permute(0, 2, 1, 3), causal, scale)
+                            v.permute(0, 2, 1, 3), causal, scale, doc_start)
     return o.permute(0, 2, 1, 3).contiguous(), lse
 
 
 def attn_bwd(q, k, v, o, do, lse, causal: bool = True,
-             scale: float | None = None):
+             scale: float | None = None, doc_start=None):
     """BSHD public contract; returns (dq, dk, dv) in BSHD."""
+    check_docs(doc_start, causal, q.shape[1], k.shape[1])
     p = lambda t: t.permute(0, 2, 1, 3)
     dq, dk, dv = _attn_bwd_bhsd(p(q), p(k), p(v), p(o), p(do), lse,
-                                causal, scale)
+                                causal, scale, doc_start)
     return (p(dq).contiguous(), p(dk).contiguous(), p(dv).contiguous())
 
 
 def _attn_fwd_bhsd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
-                   causal: bool = True, scale: float | None = None):
+                   causal: bool = True, scale: float | None = None,
+                   doc_start=None):
     """q: [B,Hq,S,D], k/v: [B,Hkv,S,D] (GQA by head repeat).
 
     Returns (o [B,Hq,S,D], lse [f32, B,Hq,S]). fp32 math.
@@ -155,10 +209,8 @@ def _attn_fwd_bhsd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
         k = k.repeat_interleave(rep, dim=1)
         v = v.repeat_interleave(rep, dim=1)
     s = torch.einsum("bhqd,bhkd->bhqk", q.float(), k.float()) * scale
-    if causal:
-        Skv = k.shape[2]
-        mask = torch.ones(S, Skv, dtype=torch.bool, device=q.device).tril(
-            diagonal=Skv - S)
+    mask = _visible(S, k.shape[2], causal, doc_start, q.device)
+    if mask is not None:
         s = s.masked_fill(~mask, float("-inf"))
     lse = torch.logsumexp(s, dim=-1)
     p = torch.exp(s - lse.unsqueeze(-1))
@@ -167,7 +219,7 @@ def _attn_fwd_bhsd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
 
 
 def _attn_bwd_bhsd(q, k, v, o, do, lse, causal: bool = True,
-                   scale: float | None = None):
+                   scale: float | None = None, doc_start=None):
     """Returns (dq, dk, dv) with GQA reduction over repeated heads."""
     B, Hq, S, D = q.shape
     Hkv = k.shape[1]
@@ -178,10 +230,8 @@ def _attn_bwd_bhsd(q, k, v, o, do, lse, causal: bool = True,
     vv = v.repeat_interleave(rep, dim=1) if Hkv != Hq else v
     qf, kf, vf, of, dof = (t.float() for t in (q, kk, vv, o, do))
     s = torch.einsum("bhqd,bhkd->bhqk", qf, kf) * scale
-    if causal:
-        Skv = kf.shape[2]
-        mask = torch.ones(S, Skv, dtype=torch.bool, device=q.device).tril(
-            diagonal=Skv - S)
+    mask = _visible(S, kf.shape[2], causal, doc_start, q.device)
+    if mask is not None:
         s = s.masked_fill(~mask, float("-inf"))
     p = torch.exp(s - lse.unsqueeze(-1))
     dv = torch.einsum("bhqk,bhqd->bhkd", p, dof)

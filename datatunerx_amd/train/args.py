@@ -54,6 +54,12 @@ class FinetuningArguments:
     bf16: bool = True
     fp16: bool = False
     gradient_checkpointing: bool = False
+    packing: bool = field(default=False, metadata={"flag": True})
+                                  # sequence packing: whole examples
+                                  # bin-packed into block_size rows,
+                                  # attention masked by document, RoPE
+                                  # restarted at each (sft and pt; refused
+                                  # with dpo). A bare `--packing` is true.
     eval_steps: int = 0
     do_predict: bool = False      # after training, greedy-generate from
                                   # the eval set's prompts and write
@@ -85,8 +91,12 @@ def _add_dataclass_args(parser: argparse.ArgumentParser, dc) -> None:
     for f in fields(dc):
         name = "--" + f.name
         if f.type in ("bool", bool) or isinstance(f.default, bool):
+            # metadata flag=True: the bare switch (no value) means true
+            kw = (dict(nargs="?", const=True)
+                  if f.metadata.get("flag") else {})
             parser.add_argument(name, type=lambda s: s.lower() in
-                                ("1", "true", "yes"), default=f.default)
+                                ("1", "true", "yes"), default=f.default,
+                                **kw)
         else:
             typ = str
             if isinstance(f.default, int):
@@ -105,4 +115,9 @@ def get_train_args(argv=None):
     def pick(dc):
         names = {f.name for f in fields(dc)}
         return dc(**{k: v for k, v in vars(ns).items() if k in names})
-    return pick(ModelArguments), pick(FinetuningArguments), pick(DataArguments)
+    margs, fargs, dargs = (pick(ModelArguments), pick(FinetuningArguments),
+                           pick(DataArguments))
+    if fargs.packing and fargs.stage == "dpo":
+        raise ValueError("--packing is not supported with --stage dpo "
+                         "(preference pairs are not packed)")
+    return margs, fargs, dargs

@@ -36,8 +36,12 @@ def main(argv=None):
     from .args import get_train_args
     from .trainer import SFTTrainer, TrainerConfig
 
-    margs, fargs, dargs = get_train_args(argv)
     status_file = os.environ.get("DTX_STATUS_FILE", "")
+    try:
+        margs, fargs, dargs = get_train_args(argv)
+    except ValueError as e:          # flag combination refused at start-up
+        write_status(status_file, "Failed", error=str(e))
+        raise SystemExit(f"error: {e}")
     rank, world, local_rank, device = init_distributed()
     if rank == 0:
         # declared-for-CR-parity flags this trainer does not act on:
@@ -154,7 +158,7 @@ def main(argv=None):
                 # pretraining: pack text blocks, train every position
                 ds = SFTDataset.from_rows_pt(
                     read_csv_rows(dargs.dataset_path, cmap), tok,
-                    cutoff_len=dargs.block_size)
+                    cutoff_len=dargs.block_size, packing=fargs.packing)
             else:
                 ds = SFTDataset.from_csv(
                     dargs.dataset_path, tok, column_map=cmap,
@@ -205,7 +209,8 @@ def main(argv=None):
             gradient_accumulation_steps=fargs.gradient_accumulation_steps,
             logging_steps=fargs.logging_steps,
             eval_steps=fargs.eval_steps, save_steps=fargs.save_steps,
-            seed=fargs.seed,
+            seed=fargs.seed, packing=fargs.packing,
+            cutoff_len=dargs.block_size,
             metrics_export_address=fargs.metrics_export_address,
             uid=fargs.uid, lora_r=fargs.lora_rank,
             lora_alpha=fargs.lora_alpha, lora_dropout=fargs.lora_dropout,

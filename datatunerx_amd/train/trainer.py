@@ -17,6 +17,7 @@ Hot loop design (MI355X-first):
 
 from __future__ import annotations
 
+import functools
 import json
 import math
 import os
@@ -27,7 +28,8 @@ from typing import Optional
 import torch
 
 from .. import ops
-from ..data.dataset import ShardedLoader
+from ..data.dataset import (DEFAULT_CUTOFF_LEN, PackedDataset,
+                            ShardedLoader, collate_packed)
 from ..models.lora import LoRALinearModule, save_adapter
 from ..parallel.ddp import GradSynchronizer, is_main, sync_scalar_mean
 
@@ -53,6 +55,10 @@ class TrainerConfig:
     optimizer_mode: str = "auto"           # auto | flat | overlap | zero1
     comm_bucket_bytes: int = 128 << 20
     seed: int = 42
+    # sequence packing: bin-pack whole training examples into rows of
+    # cutoff_len; attention is masked by document, RoPE restarts at each
+    packing: bool = False
+    cutoff_len: int = DEFAULT_CUTOFF_LEN
     metrics_export_address: Optional[str] = None
     uid: str = ""
     # checkpoint metadata (adapter_config.json)
@@ -333,9 +339,18 @@ class SFTTrainer:
         self.cfg = cfg
         self.rank, self.world = rank, world_size
         self.device = device or next(model.parameters()).device
+        collate_fn = None
+        if cfg.packing:
+            # the step count below follows the number of packed rows
+            if not isinstance(train_dataset, PackedDataset):
+                train_dataset = PackedDataset.from_dataset(
+                    train_dataset, cfg.cutoff_len, seed=cfg.seed)
+            collate_fn = functools.partial(
+                collate_packed, cutoff_len=train_dataset.cutoff_len)
         self.train_loader = ShardedLoader(
             train_dataset, cfg.micro_batch_size, rank, world_size,
-            seed=cfg.seed, pad_token_id=pad_token_id, device=self.device)
+            seed=cfg.seed, pad_token_id=pad_token_id, device=self.device,
+            collate_fn=collate_fn)
         self.eval_dataset = eval_dataset
         self.pad_token_id = pad_token_id
         sync = GradSynchronizer(world_size) if world_size > 1 else None
@@ -386,6 +401,9 @@ class SFTTrainer:
     # ------------------------------------------------------------- train
     def _micro_loss(self, mb):
         """One micro-batch's loss tensor (overridden by DPOTrainer)."""
+        if "doc_start" in mb:            # packed rows (cfg.packing)
+            return self.model(mb["input_ids"], labels=mb["labels"],
+                              doc_start=mb["doc_start"])
         return self.model(mb["input_ids"], labels=mb["labels"])
 
     def _extra_log_metrics(self) -> dict:
@@ -659,6 +677,8 @@ class DPOTrainer(SFTTrainer):
                  eval_dataset=None, pad_token_id: int = 0,
                  beta: float = 0.1):
         from ..data.preference import collate_preference
+        if cfg.packing:
+            raise ValueError("packing is not supported with stage=dpo")
         if not any(isinstance(m, LoRALinearModule)
                    for m in model.modules()):
             raise ValueError("DPO requires LoRA adapters (the frozen "

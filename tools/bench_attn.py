@@ -6,6 +6,9 @@ flops; we count the causal flops actually computed: full tiles below
 the diagonal + masked diagonal tiles).
 
   python tools/bench_attn.py --batch 64        # the bench.py shape
+  python tools/bench_attn.py --batch 4 --seq 4096 --docs 8
+      # sequence packing: 8 equal documents per row through the
+      # document-masked kernels, next to plain causal at the same S
 
 For per-kernel times run it under the profiler, in a run of its own:
   rocprofv3 --kernel-trace --stats -d OUT -- python tools/bench_attn.py --batch 64
@@ -26,8 +29,12 @@ dev = torch.device("cuda:0")
 ap = argparse.ArgumentParser()
 ap.add_argument("--batch", type=int, default=16,
                 help="batch size (bench.py's Llama-2-7B shape is 64)")
+ap.add_argument("--seq", type=int, default=1024, help="row length S")
+ap.add_argument("--docs", type=int, default=0,
+                help="N > 0: also time the document-masked kernels with "
+                     "N equal documents per row (S %% N == 0)")
 args = ap.parse_args()
-B, H, S, D = args.batch, 32, 1024, 128
+B, H, S, D = args.batch, 32, args.seq, 128
 scale = D ** -0.5
 
 q = torch.randn(B, S, H, D, device=dev, dtype=torch.bfloat16)
@@ -65,3 +72,26 @@ print(f"attn_bwd (all):              {t*1e3:7.3f} ms  {(bwd_dkdv_fl+bwd_dq_fl)/t
 t = bench(lambda: _dtx_hip.transpose_sd(q))
 gb = q.numel() * 2 * 2 / 1e9
 print(f"transpose_sd:                {t*1e3:7.3f} ms  {gb/t/1e3:6.2f} TB/s")
+
+if args.docs > 0:
+    N = args.docs
+    assert S % N == 0, "--docs must divide --seq"
+    L = S // N
+    ds = (torch.arange(S, device=dev, dtype=torch.int32) // L * L)
+    ds = ds.expand(B, S).contiguous()
+    de = ops.doc_end_from_start(ds)
+    # N causal triangles of side L instead of one of side S
+    frac = 1.0 / N
+    t_f0 = bench(lambda: _dtx_hip.attn_fwd(q, k, v, True, scale))
+    t_b0 = bench(lambda: _dtx_hip.attn_bwd(q, k, v, o, do, lse, True, scale))
+    t_f = bench(lambda: _dtx_hip.attn_fwd(q, k, v, True, scale, ds))
+    od, lsed = _dtx_hip.attn_fwd(q, k, v, True, scale, ds)
+    t_b = bench(lambda: _dtx_hip.attn_bwd(q, k, v, od, do, lsed, True,
+                                          scale, ds, de))
+    print(f"--- {N} documents of {L} per row (useful flops x{frac:.3f})")
+    print(f"attn_fwd docs (kernel only): {t_f*1e3:7.3f} ms  "
+          f"{fwd_fl*frac/t_f/1e12:6.0f} TF/s  "
+          f"plain causal {t_f0*1e3:7.3f} ms  ratio {t_f0/t_f:5.2f}x")
+    print(f"attn_bwd docs (all):         {t_b*1e3:7.3f} ms  "
+          f"{(bwd_dkdv_fl+bwd_dq_fl)*frac/t_b/1e12:6.0f} TF/s  "
+          f"plain causal {t_b0*1e3:7.3f} ms  ratio {t_b0/t_b:5.2f}x")
