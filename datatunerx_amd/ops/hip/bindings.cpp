@@ -116,13 +116,26 @@ void check_docs_shape(bool causal, long S, long Skv) {
 }
 
 // ------------------------------------------------------------- RMSNorm
-std::vector<torch::Tensor> rmsnorm_fwd(torch::Tensor x, torch::Tensor w,
-                                       double eps) {
+// The kernels hold one row in registers, at most 8 groups of 8 columns per
+// thread: H <= 8 * 8 * 256. A wider row would lose its tail silently.
+constexpr long RMSNORM_MAX_H = 8L * 8 * 256;
+
+void check_rmsnorm_row(const torch::Tensor& x, const torch::Tensor& w) {
   check_bf16_contig(x, "x");
   check_bf16_contig(w, "w");
+  TORCH_CHECK(x.dim() >= 1 && x.size(-1) > 0, "x must be [..., H]");
+  const long H = x.size(-1);
+  TORCH_CHECK(H % 8 == 0, "H % 8");
+  TORCH_CHECK(H <= RMSNORM_MAX_H, "rmsnorm: H = ", H,
+              " is above the kernel limit of ", RMSNORM_MAX_H);
+  TORCH_CHECK(w.numel() == H, "w must have H elements");
+}
+
+std::vector<torch::Tensor> rmsnorm_fwd(torch::Tensor x, torch::Tensor w,
+                                       double eps) {
+  check_rmsnorm_row(x, w);
   const int H = (int)x.size(-1);
   const long M = x.numel() / H;
-  TORCH_CHECK(H % 8 == 0, "H % 8");
   auto y = torch::empty_like(x);
   auto inv = torch::empty({M}, x.options().dtype(torch::kFloat));
   launch_rmsnorm_fwd(x.data_ptr(), w.data_ptr(), y.data_ptr(),
@@ -135,9 +148,13 @@ std::vector<torch::Tensor> rmsnorm_bwd(torch::Tensor dy, torch::Tensor x,
                                        torch::Tensor w, torch::Tensor inv,
                                        c10::optional<torch::Tensor> dres) {
   check_bf16_contig(dy, "dy");
-  check_bf16_contig(x, "x");
+  check_rmsnorm_row(x, w);
   const int H = (int)x.size(-1);
   const long M = x.numel() / H;
+  TORCH_CHECK(dy.sizes() == x.sizes(), "dy must have the shape of x");
+  TORCH_CHECK(inv.is_cuda() && inv.scalar_type() == torch::kFloat &&
+              inv.is_contiguous() && inv.numel() == M,
+              "inv must be contiguous f32 on GPU with one element per row");
   auto dx = torch::empty_like(x);
   auto dw = torch::empty({H}, x.options().dtype(torch::kFloat));
   const int nb = rmsnorm_bwd_nblocks((int)M);
@@ -203,6 +220,11 @@ torch::Tensor swiglu_fwd(torch::Tensor gate, torch::Tensor up) {
 std::vector<torch::Tensor> swiglu_bwd(torch::Tensor dout, torch::Tensor gate,
                                       torch::Tensor up) {
   check_bf16_contig(dout, "dout");
+  check_bf16_contig(gate, "gate");
+  check_bf16_contig(up, "up");
+  TORCH_CHECK(gate.numel() % 8 == 0);
+  TORCH_CHECK(up.sizes() == gate.sizes() && dout.sizes() == gate.sizes(),
+              "dout, gate and up must have one shape");
   auto dg = torch::empty_like(gate);
   auto du = torch::empty_like(up);
   launch_swiglu_bwd(dout.data_ptr(), gate.data_ptr(), up.data_ptr(),

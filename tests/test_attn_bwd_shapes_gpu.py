@@ -6,13 +6,17 @@ stage's lse/delta in its prefetch; dq computes delta in its prologue.
 These cases sit on the edges of that scheme: less than one tile, one row
 into a second 64-row stage, a second kv block, an odd stage count under
 GQA, D=64 ragged, non-causal with a kv tail. Same metric and 3e-2 bound
-as tests/test_ops_gpu.py::test_attn_bwd, fp32 CPU reference.
+as tests/test_ops_gpu.py::test_attn_bwd, fp32 CPU reference; beside it the
+row-wise bound of tests/kernel_check.py against fp64, which also covers the
+forward's o and lse at these shapes.
 """
 
 import math
 
 import pytest
 import torch
+
+import kernel_check as kc
 
 pytestmark = pytest.mark.gpu
 
@@ -36,7 +40,8 @@ def assert_close(got, want, rtol, name):
 
 
 def make_case(B, Hq, Hkv, S, D, causal, seed):
-    """CPU bf16 inputs plus the fp32 reference gradients."""
+    """CPU bf16 inputs, the fp32 reference gradients and the fp64
+    reference with its budgets."""
     gen = torch.Generator().manual_seed(seed)
     q = mk(gen, B, S, Hq, D)
     k = mk(gen, B, S, Hkv, D)
@@ -44,12 +49,13 @@ def make_case(B, Hq, Hkv, S, D, causal, seed):
     do = mk(gen, B, S, Hq, D)
     o_ref, lse_ref = ref.attn_fwd(q, k, v, causal)
     grads = ref.attn_bwd(q, k, v, o_ref, do, lse_ref, causal)
-    return (q, k, v, do), grads
+    return (q, k, v, do), grads, kc.attn_ref64(q, k, v, do, causal)
 
 
-def check(got, want):
+def check(got, want, o, lse, want64):
     for g, w, name in zip(got, want, ("attn dq", "attn dk", "attn dv")):
         assert_close(g.cpu(), w, rtol=3e-2, name=name)
+    kc.check_attn(dict(zip(("dq", "dk", "dv"), got), o=o, lse=lse), want64)
 
 
 @pytest.mark.parametrize("B,Hq,Hkv,S,D,causal", [
@@ -61,12 +67,13 @@ def check(got, want):
     (1, 2, 2, 320, 128, False),      # non-causal, 5 stages, kv tail of 64
 ])
 def test_attn_bwd_shapes(B, Hq, Hkv, S, D, causal):
-    (q, k, v, do), want = make_case(B, Hq, Hkv, S, D, causal, seed=S + D)
+    (q, k, v, do), want, want64 = make_case(B, Hq, Hkv, S, D, causal,
+                                            seed=S + D)
     q, k, v, do = (t.to(DEV) for t in (q, k, v, do))
     scale = 1.0 / math.sqrt(D)
     o, lse = ops.attn_fwd(q, k, v, causal, scale)
     got = ops.attn_bwd(q, k, v, o, do, lse, causal, scale)
-    check(got, want)
+    check(got, want, o, lse, want64)
     # no atomics anywhere in the backward: a second run is bit-equal
     again = ops.attn_bwd(q, k, v, o, do, lse, causal, scale)
     for a, b, name in zip(got, again, ("dq", "dk", "dv")):
@@ -79,7 +86,8 @@ def test_attn_bwd_poisoned_tail(S):
     a read past row S, or a clamped row that leaked into the math, shows
     up as a non-finite gradient."""
     B, H, D, causal = 1, 2, 128, True
-    (q, k, v, do), want = make_case(B, H, H, S, D, causal, seed=1000 + S)
+    (q, k, v, do), want, want64 = make_case(B, H, H, S, D, causal,
+                                            seed=1000 + S)
     scale = 1.0 / math.sqrt(D)
     o, lse = ops.attn_fwd(q.to(DEV), k.to(DEV), v.to(DEV), causal, scale)
 
@@ -95,4 +103,4 @@ def test_attn_bwd_poisoned_tail(S):
     got = ops.attn_bwd(qp, kp, vp, op, dop, lse, causal, scale)
     for g, name in zip(got, ("dq", "dk", "dv")):
         assert torch.isfinite(g.float()).all(), f"{name} not finite"
-    check(got, want)
+    check(got, want, o, lse, want64)

@@ -8,6 +8,8 @@ import math
 import pytest
 import torch
 
+import kernel_check as kc
+
 pytestmark = pytest.mark.gpu
 
 if torch.cuda.is_available():
@@ -230,6 +232,9 @@ def test_attn_fwd(B, Hq, Hkv, S, Skv, D, causal):
     o_ref, lse_ref = ref.attn_fwd(q.cpu(), k.cpu(), v.cpu(), causal)
     assert_close(o.cpu(), o_ref, name="attn o")
     assert_close(lse.cpu(), lse_ref, rtol=1e-2, name="attn lse")
+    # per row against fp64, lse to 2^-12 (docs/kernels.md, Numerics bounds)
+    want = kc.attn_ref64(q, k, v, None, causal)
+    kc.check_attn({"o": o, "lse": lse}, want, ("o",))
 
 
 @pytest.mark.parametrize("B,Hq,Hkv,S,D,causal", [
@@ -254,6 +259,8 @@ def test_attn_bwd(B, Hq, Hkv, S, D, causal):
     assert_close(dq.cpu(), dq_r, rtol=3e-2, name="attn dq")
     assert_close(dk.cpu(), dk_r, rtol=3e-2, name="attn dk")
     assert_close(dv.cpu(), dv_r, rtol=3e-2, name="attn dv")
+    want = kc.attn_ref64(q, k, v, do, causal)
+    kc.check_attn({"o": o, "lse": lse, "dq": dq, "dk": dk, "dv": dv}, want)
 
 
 @pytest.mark.parametrize("B,S,H,D", [(2, 128, 4, 128), (1, 100, 2, 64)])
@@ -355,6 +362,8 @@ def test_attn_decode(B, Hq, Hkv, Skv, D):
     assert_close(o.cpu(), o_ref, name="decode o")
     assert_close(lse.cpu().reshape(-1), lse_ref.reshape(-1), rtol=1e-2,
                  name="decode lse")
+    want = kc.attn_ref64(q, k, v, None, False)   # S=1 sees the whole cache
+    kc.check_attn({"o": o, "lse": lse}, want, ("o",), tag="decode ")
 
 
 @pytest.mark.parametrize("N,K", [(4096, 4096), (32000, 4096),

@@ -3,12 +3,16 @@ forward / dq / dkdv kernels and of the RoPE kernel against the fp32
 reference with doc_start, plus bit-reproducibility, isolation between
 documents, agreement with the plain causal kernel per document, and the
 model / trainer plumbing. Metric and bounds are those of
-tests/test_ops_gpu.py (max error relative to the reference's max)."""
+tests/test_ops_gpu.py (max error relative to the reference's max); the
+comparisons with a reference also get the row-wise bound of
+tests/kernel_check.py against fp64."""
 
 import math
 
 import pytest
 import torch
+
+import kernel_check as kc
 
 pytestmark = pytest.mark.gpu
 
@@ -64,8 +68,9 @@ _CACHE = {}
 
 
 def case(name):
-    """Inputs, GPU results and the fp32 reference of a case, computed
-    once and shared (read-only) by every test that needs them."""
+    """Inputs, GPU results, the fp32 reference and the fp64 reference (with
+    its budgets) of a case, computed once and shared (read-only) by every
+    test that needs them."""
     if name in _CACHE:
         return _CACHE[name]
     B, Hq, Hkv, S, D, lens = CASES[name]
@@ -82,6 +87,8 @@ def case(name):
                                     c["v"].float(), o_r, c["do"].float(),
                                     lse_r, True, None, c["ds"])
     want = {"o": o_r, "lse": lse_r, "dq": dq_r, "dk": dk_r, "dv": dv_r}
+    want["f64"] = kc.attn_ref64(c["q"], c["k"], c["v"], c["do"], True,
+                                doc_start=c["ds"])
     _CACHE[name] = (t, got, want)
     return _CACHE[name]
 
@@ -93,6 +100,7 @@ def test_attn_docs_vs_reference(name):
     assert_close(got["lse"].cpu(), want["lse"], rtol=1e-2, name="lse")
     for k in ("dq", "dk", "dv"):
         assert_close(got[k].cpu(), want[k], rtol=3e-2, name=k)
+    kc.check_attn(got, want["f64"], tag=name + " ")
 
 
 @pytest.mark.parametrize("name", list(CASES))
@@ -190,6 +198,10 @@ def test_rope_docs(D):
                  rtol=2e-2, name="rope fwd")
     assert_close(dx.cpu(), ref.rope_bwd(dy.float(), cos, sin, 3, ds),
                  rtol=2e-2, name="rope bwd")
+    pos = 3 + torch.arange(S).view(1, S) - ds.long()
+    for got, src, bwd in ((y, x, False), (dx, dy, True)):
+        w64, bud = kc.rope_ref64(src, cos, sin, pos, backward=bwd)
+        kc.assert_elems(got, w64, 2.0 ** -8 * bud, name="rope docs")
 
 
 def _mini(seed=0):
