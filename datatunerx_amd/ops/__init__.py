@@ -380,6 +380,43 @@ def mlora_add(y, x, A, Bt, scale, idx):
     return ref.mlora_add(y, x, A, Bt, scale, idx)
 
 
+# ------------------------------------------------------------ sampling
+def sample(logits, temperature, top_p, top_k, seed, offset, u=None):
+    """One token per row of logits [B, V], each row with its own
+    temperature / top_p (fp32 [B]), top_k (int32 [B]) and RNG stream
+    (seed int64 [B], offset int32 [B]: the row's token counter) -> int64
+    [B]. The contract is ref.sample's; u (fp32 [B] in [0, 1)) replaces
+    the RNG. On the GPU everything is read by the kernel only (no host
+    sync: hipGraph-capturable); logits must be bf16 with V % 8 == 0, a
+    row stride % 8 == 0 and V <= sample_max_vocab()."""
+    if _gpu(logits):
+        # the binding checks the contract and refuses the rest
+        return _EXT.sample(logits, temperature, top_p, top_k, seed, offset,
+                           u)
+    if logits.dim() != 2 or logits.stride(1) != 1:
+        raise ValueError("sample: logits must be [B, V] with dense rows")
+    B = logits.shape[0]
+    for name, t, dt in (("temperature", temperature, torch.float32),
+                        ("top_p", top_p, torch.float32),
+                        ("top_k", top_k, torch.int32),
+                        ("seed", seed, torch.int64),
+                        ("offset", offset, torch.int32),
+                        ("u", u, torch.float32)):
+        if t is None and name == "u":
+            continue
+        if not (tuple(t.shape) == (B,) and t.dtype == dt
+                and t.device == logits.device):
+            raise ValueError(
+                f"sample: {name} must be {dt} [{B}] on the logits' device, "
+                f"got {t.dtype} {tuple(t.shape)} on {t.device}")
+    return ref.sample(logits, temperature, top_p, top_k, seed, offset, u)
+
+
+def sample_max_vocab() -> int:
+    """Widest row the sampling kernel holds in registers."""
+    return 19 * 8 * 1024
+
+
 # -------------------------------------------------- weight dequant
 def dequant_int8(q, scale):
     if _gpu(q):

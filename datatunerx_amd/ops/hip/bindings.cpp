@@ -71,6 +71,10 @@ void launch_mlora_expand_add(void*, const float*, const void*, const float*,
                              const int*, int, int, int, int, hipStream_t);
 void launch_gemm_nt(const void*, const void*, const void*, void*, long,
                     int, int, hipStream_t);
+long sample_max_vocab();
+void launch_sample(const void*, long, int, int, const float*, const float*,
+                   const int*, const long long*, const int*, const float*,
+                   long long*, hipStream_t);
 void launch_attn_decode(const void*, const void*, const void*,
                         const int*, float*, void*, float*, int, int, int,
                         int, int, float, int, hipStream_t);
@@ -669,6 +673,55 @@ void mlora_add(torch::Tensor y, torch::Tensor x, torch::Tensor A,
                           (int)M, (int)N, (int)R, (int)G, cur_stream());
 }
 
+// Per-row sampling of a decode batch (sample.hip): every parameter is a
+// device tensor the kernel reads at run time and the only allocation is
+// the output, so the call is hipGraph-capturable and a replay follows
+// whatever the parameter buffers hold by then.
+torch::Tensor sample(torch::Tensor logits, torch::Tensor temperature,
+                     torch::Tensor top_p, torch::Tensor top_k,
+                     torch::Tensor seed, torch::Tensor offset,
+                     c10::optional<torch::Tensor> u) {
+  TORCH_CHECK(logits.is_cuda() && logits.scalar_type() == torch::kBFloat16,
+              "sample: logits must be bf16 on the GPU");
+  TORCH_CHECK(logits.dim() == 2, "sample: logits must be [B, V]");
+  const long B = logits.size(0), V = logits.size(1);
+  TORCH_CHECK(V > 0 && V % 8 == 0, "sample: V % 8, got V = ", V);
+  TORCH_CHECK(V <= sample_max_vocab(), "sample: V = ", V,
+              " is above the kernel limit of ", sample_max_vocab());
+  TORCH_CHECK(logits.stride(1) == 1, "sample: logits rows must be dense");
+  TORCH_CHECK(B <= 1 || (logits.stride(0) >= 0 && logits.stride(0) % 8 == 0),
+              "sample: row stride % 8");
+  TORCH_CHECK((uintptr_t)logits.data_ptr() % 16 == 0,
+              "sample: logits need 16-B alignment");
+  auto par = [&](const torch::Tensor& t, torch::ScalarType ty,
+                 const char* name) {
+    TORCH_CHECK(t.is_cuda() && t.get_device() == logits.get_device() &&
+                t.scalar_type() == ty && t.dim() == 1 && t.size(0) == B &&
+                t.is_contiguous(),
+                "sample: ", name, " must be a contiguous ", ty, " [", B,
+                "] tensor on the logits' device");
+  };
+  par(temperature, torch::kFloat, "temperature");
+  par(top_p, torch::kFloat, "top_p");
+  par(top_k, torch::kInt, "top_k");
+  par(seed, torch::kLong, "seed");
+  par(offset, torch::kInt, "offset");
+  const float* up = nullptr;
+  if (u.has_value()) {
+    par(*u, torch::kFloat, "u");
+    up = u->data_ptr<float>();
+  }
+  auto out = torch::empty({B}, logits.options().dtype(torch::kLong));
+  if (B == 0) return out;
+  launch_sample(logits.data_ptr(), B > 1 ? logits.stride(0) : V, (int)B,
+                (int)V, temperature.data_ptr<float>(),
+                top_p.data_ptr<float>(), top_k.data_ptr<int>(),
+                (const long long*)seed.data_ptr<int64_t>(),
+                offset.data_ptr<int>(), up,
+                (long long*)out.data_ptr<int64_t>(), cur_stream());
+  return out;
+}
+
 // Decode fast path: q [B,1,Hq,D] against the KV cache (flash-decoding
 // split-KV partials; no V transpose needed).
 std::vector<torch::Tensor> attn_decode(torch::Tensor q, torch::Tensor k,
@@ -812,6 +865,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("scale"), py::arg("group") = 64);
   m.def("mlora_add", &mlora_add, py::arg("y"), py::arg("x"), py::arg("A"),
         py::arg("Bt"), py::arg("scale"), py::arg("idx"));
+  m.def("sample", &sample, py::arg("logits"), py::arg("temperature"),
+        py::arg("top_p"), py::arg("top_k"), py::arg("seed"),
+        py::arg("offset"), py::arg("u") = py::none());
+  m.def("sample_max_vocab", &sample_max_vocab);
   m.def("gemm_nt", &gemm_nt, py::arg("a"), py::arg("b"),
         py::arg("src") = py::none());
   m.def("attn_decode", &attn_decode, py::arg("q"), py::arg("k"),

@@ -424,3 +424,66 @@ def xent_dlogits(logits_c, targets, lse, v0: int,
         dl[idx, (targets[idx] - v0)] -= 1.0
     dl[targets == ignore_index] = 0.0
     return dl.to(logits_c.dtype)
+
+
+# ------------------------------------------------------------- sampling
+def sample_rng(seed: torch.Tensor, offset: torch.Tensor) -> torch.Tensor:
+    """The sampler's random bits, int64 [B] in [0, 2^24): the splitmix64
+    finalizer of dropout_mask over z = seed + (offset + 1) * GAMMA
+    (mod 2^64), top 24 bits. Keyed by a row's own (seed, offset) only.
+    Integer arithmetic, so it is the GPU kernel's value bit for bit."""
+    def _u(c):
+        return c - (1 << 64) if c >= (1 << 63) else c
+
+    def _lshr(z, k):
+        return (z >> k) & ((1 << (64 - k)) - 1)
+
+    z = seed.to(torch.int64) + (offset.to(torch.int64) + 1) * \
+        _u(0x9E3779B97F4A7C15)
+    z = z ^ _lshr(z, 30)
+    z = z * _u(0xBF58476D1CE4E5B9)
+    z = z ^ _lshr(z, 27)
+    z = z * _u(0x94D049BB133111EB)
+    z = z ^ _lshr(z, 31)
+    return _lshr(z, 40)
+
+
+def sample(logits: torch.Tensor, temperature: torch.Tensor,
+           top_p: torch.Tensor, top_k: torch.Tensor, seed: torch.Tensor,
+           offset: torch.Tensor, u=None) -> torch.Tensor:
+    """fp32 twin of the sampling kernel (sample.hip), every row with its
+    own parameters -> int64 [B].
+
+    temperature <= 0: first index of the row maximum. Otherwise, in the
+    order (logit descending, index ascending) and with the weights
+    w = exp((l - l_max) / temperature): the candidates are the first
+    top_k (all when top_k <= 0 or >= V); the nucleus is their longest
+    prefix whose weight sum is <= top_p * Z_C (Z_C: the candidates' sum;
+    all candidates when top_p >= 1), never fewer than one; the token is
+    the first nucleus member, in INDEX order, whose running weight sum
+    exceeds u * Z_N (the last member when rounding leaves none). u is
+    sample_rng(seed, offset) * 2^-24 unless given."""
+    B, V = logits.shape
+    if u is None:
+        u = sample_rng(seed, offset).to(torch.float32) * (2.0 ** -24)
+    x = logits.float()
+    T = temperature.float().view(B, 1)
+    greedy = ~(T > 0)
+    w = torch.exp((x - x.max(1, keepdim=True).values) /
+                  torch.where(greedy, torch.ones_like(T), T))
+    _, order = torch.sort(x, dim=1, descending=True, stable=True)
+    k = top_k.view(B, 1).to(torch.int64)
+    k = torch.where((k <= 0) | (k >= V), torch.full_like(k, V), k)
+    cand = torch.arange(V, device=x.device).view(1, V) < k
+    cum = torch.cumsum(torch.gather(w, 1, order) * cand, dim=1)
+    p = top_p.float().view(B, 1)
+    keep = cand & ((cum <= p * cum[:, -1:]) | (p >= 1))
+    keep[:, 0] = True
+    member = torch.zeros_like(keep).scatter_(1, order, keep)
+    cdf = torch.cumsum(w * member, dim=1)
+    target = u.float().view(B, 1) * cdf[:, -1:]
+    hit = member & (cdf > target)
+    first = hit.to(torch.int8).argmax(1)
+    last = V - 1 - member.flip(1).to(torch.int8).argmax(1)
+    tok = torch.where(hit.any(1), first, last)
+    return torch.where(greedy.view(B), x.argmax(1), tok)

@@ -17,6 +17,7 @@ import copy
 import json
 import math
 import os
+import random
 from typing import List, Optional
 
 import torch
@@ -91,7 +92,12 @@ class _DecodeState:
     every method keeps len32 == pos + 1, so a device-mode update never
     attends an empty row. Batched decode shares one weight stream across
     the batch — single-stream decode is WEIGHT-bandwidth-bound, so this
-    is the scaling axis for serving throughput."""
+    is the scaling axis for serving throughput.
+
+    The rows' sampling parameters are device state too (temperature,
+    top_p, top_k, seed, and offset: the number of tokens the row has
+    sampled, its RNG counter), so ops.sample draws every row of a step
+    with that row's own setting; all-zero (the start) is greedy."""
 
     def __init__(self, B, Hkv, max_s, D, layers, device, dtype):
         self.B, self.max_s = B, max_s
@@ -99,6 +105,12 @@ class _DecodeState:
         self.wpos = self._row0.clone()
         self.pos32 = torch.zeros(B, dtype=torch.int32, device=device)
         self.len32 = torch.ones(B, dtype=torch.int32, device=device)
+        self.temperature = torch.zeros(B, dtype=torch.float32,
+                                       device=device)
+        self.top_p = torch.ones(B, dtype=torch.float32, device=device)
+        self.top_k = torch.zeros(B, dtype=torch.int32, device=device)
+        self.seed = torch.zeros(B, dtype=torch.int64, device=device)
+        self.offset = torch.zeros(B, dtype=torch.int32, device=device)
         self.caches = [KVCache(B, Hkv, max_s, D, device, dtype,
                                wpos=self.wpos, len32=self.len32)
                        for _ in range(layers)]
@@ -111,6 +123,21 @@ class _DecodeState:
         self.pos32.copy_(pos)
         self.len32.copy_(pos + 1)
 
+    def set_sampling(self, samp, offset: int = 1):
+        """Per-row sampling parameters (a _Sampling of B rows). offset:
+        tokens every row has sampled already — 1 after prefill, whose
+        first token is drawn with offset 0."""
+        self.temperature.copy_(torch.tensor(samp.temperature,
+                                            dtype=torch.float32))
+        self.top_p.copy_(torch.tensor(samp.top_p, dtype=torch.float32))
+        self.top_k.copy_(torch.tensor(samp.top_k, dtype=torch.int32))
+        self.seed.copy_(torch.tensor(samp.seed, dtype=torch.int64))
+        self.offset.fill_(offset)
+
+    def sample_args(self):
+        return (self.temperature, self.top_p, self.top_k, self.seed,
+                self.offset)
+
     def reset(self):
         """Empty rows. No cache zeroing needed: prefill overwrites rows
         up to their length and attention never reads past len32."""
@@ -122,6 +149,7 @@ class _DecodeState:
         self.wpos += 1
         self.pos32 += 1
         self.len32 += 1
+        self.offset += 1
 
 
 class _GraphedDecoder(_DecodeState):
@@ -132,9 +160,12 @@ class _GraphedDecoder(_DecodeState):
     serves every sequence length and adapter assignment. Built once per
     engine (under the capture lock) and reset per request; a batch pads
     to B with dummy rows. The graph's static outputs are `logits`
-    [B, 1, V] and `out` [B], its greedy argmax."""
+    [B, 1, V] and `out` [B]: the greedy argmax, or with `sample` the
+    token ops.sample draws for each row from the state's sampling
+    buffers (a row at temperature 0 gets the same argmax, bit for bit),
+    so one graph serves every mix of greedy and sampled rows."""
 
-    def __init__(self, model, cfg, device, B, max_s):
+    def __init__(self, model, cfg, device, B, max_s, sample=False):
         super().__init__(B, cfg.num_key_value_heads, max_s, cfg.head_dim,
                          cfg.num_hidden_layers, device,
                          next(model.parameters()).dtype)
@@ -145,6 +176,10 @@ class _GraphedDecoder(_DecodeState):
         def forward():
             logits = model(self.input, pos_dev=self.pos32,
                            kv_caches=self.caches, **akw)
+            if sample:
+                from .. import ops
+                return logits, ops.sample(logits[:, -1],
+                                          *self.sample_args())
             return logits, logits[:, -1].argmax(-1)
 
         with torch.no_grad():
@@ -276,6 +311,42 @@ def build_model(name: str, device, adapter_dir: Optional[str] = None,
     return model
 
 
+class _Sampling:
+    """Per-row sampling parameters of one generation: lists of
+    temperature, top_p, top_k and seed (one entry a row), and `plain`:
+    the row named neither a seed nor a top_k, so a host-sampling engine
+    draws it from the torch RNG the way it always did."""
+
+    def __init__(self, temperature, top_p, top_k, seed, plain):
+        self.temperature, self.top_p = temperature, top_p
+        self.top_k, self.seed, self.plain = top_k, seed, plain
+
+    def __len__(self):
+        return len(self.temperature)
+
+    @property
+    def greedy(self) -> bool:
+        return not any(t > 0 for t in self.temperature)
+
+    def padded(self, n: int):
+        """Extended to n rows with greedy dummy rows."""
+        k = n - len(self)
+        return _Sampling(self.temperature + [0.0] * k,
+                         self.top_p + [1.0] * k, self.top_k + [0] * k,
+                         self.seed + [0] * k, self.plain + [True] * k)
+
+    def tensors(self, device, offset: int = 0):
+        """ops.sample's parameter tensors, every row at `offset`."""
+        n = len(self)
+        return (torch.tensor(self.temperature, dtype=torch.float32,
+                             device=device),
+                torch.tensor(self.top_p, dtype=torch.float32,
+                             device=device),
+                torch.tensor(self.top_k, dtype=torch.int32, device=device),
+                torch.tensor(self.seed, dtype=torch.int64, device=device),
+                torch.full((n,), offset, dtype=torch.int32, device=device))
+
+
 class InferenceEngine:
     """One generation context over a (shared, read-only) model. For
     concurrent serving, build several engines over the SAME model
@@ -304,6 +375,18 @@ class InferenceEngine:
                           self.device.type == "cuda" and
                           not dist.is_initialized() and
                           os.environ.get("DTX_NO_GRAPH") != "1")
+        # Sampling on the device (ops.sample inside the decode step, each
+        # row with its own parameters): llama on one GPU, with logits the
+        # kernel takes. Everywhere else the host sampler, as before.
+        from .. import ops
+        vocab = getattr(getattr(model, "cfg", None), "vocab_size", 0)
+        self.device_sampling = (
+            self.is_llama and self.device.type == "cuda" and
+            not dist.is_initialized() and
+            next(model.parameters()).dtype == torch.bfloat16 and
+            vocab % 8 == 0 and 0 < vocab <= ops.sample_max_vocab())
+        # seeds of the requests that name none
+        self._seed_rng = random.Random()
         # stop set: tokenizer eos (may be a LIST in llama3-style
         # config.json), plus any template stop_words that the tokenizer
         # encodes to a single special id (llama3's <|eot_id|> ends a
@@ -369,7 +452,8 @@ class InferenceEngine:
         try:
             with InferenceEngine._capture_lock, self._stream_ctx():
                 return _GraphedDecoder(self.model, self.model.cfg,
-                                       self.device, B, max_s)
+                                       self.device, B, max_s,
+                                       sample=self.device_sampling)
         except Exception:
             return None
 
@@ -433,19 +517,24 @@ class InferenceEngine:
 
     def chat(self, messages: List[dict], max_tokens: int = 64,
              temperature: float = 0.0, top_p: float = 1.0,
-             adapter: Optional[str] = None) -> str:
+             adapter: Optional[str] = None, top_k: int = 0,
+             seed: Optional[int] = None) -> str:
         """messages: [{role, content}] -> completion text. adapter: name
-        of an attached adapter (None: the base model)."""
+        of an attached adapter (None: the base model). top_k: sample
+        among the k most likely tokens (0: all). seed: makes a sampled
+        completion reproducible — the same request with the same seed
+        returns the same tokens, whatever it shares a batch with."""
         self._adapter_index(adapter)
         with self._stream_ctx():
             ids = self.generate(self._encode_messages(messages),
                                 max_tokens, temperature, top_p,
-                                adapter=adapter)
+                                adapter=adapter, top_k=top_k, seed=seed)
             return self.tok.decode(ids)
 
     def chat_stream(self, messages: List[dict], max_tokens: int = 64,
                     temperature: float = 0.0, top_p: float = 1.0,
-                    adapter: Optional[str] = None):
+                    adapter: Optional[str] = None, top_k: int = 0,
+                    seed: Optional[int] = None):
         """Like chat() but yields text DELTAS as tokens decode (the
         serving endpoint streams these as SSE chunks). Token-identical
         to chat(): same generate loop, so TP followers running chat()
@@ -454,7 +543,7 @@ class InferenceEngine:
         ids, sent = [], ""
         for tok_id in self.generate_stream(
                 self._encode_messages(messages), max_tokens, temperature,
-                top_p, adapter=adapter):
+                top_p, adapter=adapter, top_k=top_k, seed=seed):
             ids.append(tok_id)
             delta, sent = self._delta(ids, sent)
             if delta:
@@ -466,25 +555,71 @@ class InferenceEngine:
     @torch.no_grad()
     def generate(self, prompt_ids: List[int], max_new_tokens: int = 64,
                  temperature: float = 0.0, top_p: float = 1.0,
-                 adapter: Optional[str] = None) -> List[int]:
+                 adapter: Optional[str] = None, top_k: int = 0,
+                 seed: Optional[int] = None) -> List[int]:
         return list(self.generate_stream(prompt_ids, max_new_tokens,
                                          temperature, top_p,
-                                         adapter=adapter))
+                                         adapter=adapter, top_k=top_k,
+                                         seed=seed))
 
     @torch.no_grad()
     def generate_stream(self, prompt_ids: List[int],
                         max_new_tokens: int = 64, temperature: float = 0.0,
-                        top_p: float = 1.0, adapter: Optional[str] = None):
+                        top_p: float = 1.0, adapter: Optional[str] = None,
+                        top_k: int = 0, seed: Optional[int] = None):
         gi = self._adapter_index(adapter)
+        samp = self._sampling(1, temperature, top_p, top_k, seed)
         with self._stream_ctx():
             yield from self._generate_stream(prompt_ids, max_new_tokens,
-                                             temperature, top_p, gi)
+                                             samp, gi)
+
+    # ------------------------------------------------------- sampling
+    def _sampling(self, n: int, temperature, top_p, top_k=0, seed=None):
+        """_Sampling of n rows; each argument is a scalar or a per-row
+        list. A sampled row that names no seed gets one from the
+        engine's own generator — except a plain row (no seed, no top_k)
+        of a host-sampling engine, which stays on the torch RNG."""
+        def rows(v, cast, name):
+            if isinstance(v, (list, tuple)):
+                if len(v) != n:
+                    raise ValueError(
+                        f"{len(v)} {name} values for {n} prompts")
+                return [cast(x) for x in v]
+            return [cast(v)] * n
+
+        t = rows(temperature, float, "temperature")
+        p = rows(top_p, float, "top_p")
+        k = rows(top_k, lambda x: max(int(x or 0), 0), "top_k")
+        s = rows(seed, lambda x: None if x is None else int(x), "seed")
+        plain = [si is None and ki == 0 for si, ki in zip(s, k)]
+        for i in range(n):
+            if s[i] is None:
+                drawn = t[i] > 0 and (self.device_sampling or not plain[i])
+                s[i] = self._seed_rng.getrandbits(63) if drawn else 0
+            else:       # any Python int, as the int64 with the same bits
+                s[i] = (s[i] + (1 << 63)) % (1 << 64) - (1 << 63)
+        return _Sampling(t, p, k, s, plain)
+
+    def _device_sample(self, logits, samp, offset: int) -> torch.Tensor:
+        """ops.sample over the rows of logits [B, V] on the GPU, every
+        row with its own parameters and all at token counter `offset`."""
+        from .. import ops
+        return ops.sample(logits, *samp.tensors(self.device, offset))
+
+    def _host_sample(self, logits, samp, i: int, offset: int) -> int:
+        """Row i's token `offset` from its logits [V] on a host-sampling
+        engine: plain rows through the torch RNG as ever, rows with a
+        seed or a top_k through ops.sample's CPU reference."""
+        if samp.plain[i]:
+            return self._sample(logits, samp.temperature[i], samp.top_p[i])
+        return self._sample(logits, samp.temperature[i], samp.top_p[i],
+                            samp.top_k[i], samp.seed[i], offset)
 
     @torch.no_grad()
-    def _generate_stream(self, prompt_ids: List[int],
-                         max_new_tokens: int = 64,
-                         temperature: float = 0.0, top_p: float = 1.0,
-                         gi: int = -1):
+    def _generate_stream(self, prompt_ids: List[int], max_new_tokens: int,
+                         samp, gi: int = -1):
+        """samp: the request's _Sampling (one row). Token n is drawn with
+        RNG offset n on every path."""
         if not prompt_ids:
             raise ValueError("empty prompt")
         akw = self._selection([gi])
@@ -495,6 +630,13 @@ class InferenceEngine:
                 f"context ({limit} positions)")
         ids = torch.tensor([prompt_ids], dtype=torch.long,
                            device=self.device)
+        dev = self.device_sampling
+
+        def pick(logits, n):        # logits [1, S, V] -> token n
+            if dev:
+                return int(self._device_sample(logits[:, -1], samp, n))
+            return self._host_sample(logits[0, -1], samp, 0, n)
+
         n_out = 0
         gd = self._get_graphed() if self.is_llama else None
         if gd is not None and len(prompt_ids) + max_new_tokens + 1 < \
@@ -503,9 +645,10 @@ class InferenceEngine:
             # caches, then one graph replay per token
             gd.reset()
             gd.set_adapters([gi])
+            gd.set_sampling(samp)
             logits = self.model(ids, pos0=0, kv_caches=gd.caches, **akw)
             gd.set_state([len(prompt_ids)])
-            nxt = self._sample(logits[0, -1], temperature, top_p)
+            nxt = pick(logits, 0)
             for _ in range(max_new_tokens):
                 if self._is_stop(nxt):
                     break
@@ -514,9 +657,10 @@ class InferenceEngine:
                 if len(prompt_ids) + n_out + 1 >= gd.max_s:
                     break
                 gd.step(nxt)
-                # sampled from the logits, not gd.out: one tie-breaking
-                # rule for graphed and eager decode
-                nxt = self._sample(gd.logits[0, -1], temperature, top_p)
+                # device sampling: the graph drew the token (gd.out, the
+                # same kernel as the eager path). Host sampling: from
+                # the logits, one tie-breaking rule for graphed and eager
+                nxt = int(gd.out[0]) if dev else pick(gd.logits, n_out)
             return
         if self.is_llama:
             cfg = self.model.cfg
@@ -528,13 +672,13 @@ class InferenceEngine:
                       for _ in range(cfg.num_hidden_layers)]
             pos = 0
             cur = ids
-            for _ in range(max_new_tokens):
+            for n in range(max_new_tokens):
                 logits = self.model(cur, pos0=pos, kv_caches=caches,
                                     **akw)
                 pos += cur.shape[1]
                 if pos >= max_s:
                     break
-                nxt = self._sample(logits[0, -1], temperature, top_p)
+                nxt = pick(logits, n)
                 if self._is_stop(nxt):
                     break
                 yield nxt
@@ -542,18 +686,22 @@ class InferenceEngine:
                                    device=self.device)
         else:
             seq = list(prompt_ids)
-            for _ in range(max_new_tokens):
+            for n in range(max_new_tokens):
                 cur = torch.tensor([seq], dtype=torch.long,
                                    device=self.device)
                 logits = self.model(cur)
-                nxt = self._sample(logits[0, -1], temperature, top_p)
+                nxt = pick(logits, n)
                 if self._is_stop(nxt):
                     break
                 yield nxt
                 seq.append(nxt)
 
     def _sample(self, logits: torch.Tensor, temperature: float,
-                top_p: float) -> int:
+                top_p: float, top_k: int = 0, seed: Optional[int] = None,
+                offset: int = 0) -> int:
+        """The host sampler. With neither seed nor top_k: the torch RNG.
+        With either: ops.sample's CPU reference on this row, keyed by
+        (seed, offset), so a seed means the same on every engine."""
         import torch.distributed as dist
         tp = dist.is_initialized() and dist.get_world_size() > 1
         comm_dev = (self.device if tp and dist.get_backend() == "nccl"
@@ -563,7 +711,16 @@ class InferenceEngine:
             t = torch.zeros(1, dtype=torch.long, device=comm_dev)
             dist.broadcast(t, src=0)
             return int(t)
-        if temperature <= 0.0:
+        if seed is not None or top_k > 0:
+            from .. import ops
+            nxt = int(ops.sample(
+                logits.detach().float().cpu().view(1, -1),
+                torch.tensor([temperature], dtype=torch.float32),
+                torch.tensor([top_p], dtype=torch.float32),
+                torch.tensor([top_k], dtype=torch.int32),
+                torch.tensor([seed or 0], dtype=torch.int64),
+                torch.tensor([offset], dtype=torch.int32))[0])
+        elif temperature <= 0.0:
             nxt = int(logits.argmax())
         else:
             probs = torch.softmax(logits.float() / temperature, dim=-1)
@@ -585,19 +742,21 @@ class InferenceEngine:
     @torch.no_grad()
     def generate_batch(self, prompts: List[List[int]],
                        max_new_tokens: int = 64,
-                       temperature: float = 0.0,
-                       top_p: float = 1.0,
-                       adapters: Optional[List[Optional[str]]] = None
-                       ) -> List[List[int]]:
+                       temperature=0.0, top_p=1.0,
+                       adapters: Optional[List[Optional[str]]] = None,
+                       top_k=0, seed=None) -> List[List[int]]:
         """Ragged batched generation: per-row prefill, then ONE decode
         step per token for the whole batch (the weight stream is read
         once per step instead of once per request). adapters: one
         adapter name (or None: base model) per prompt — rows of one
-        batch may use different adapters."""
+        batch may use different adapters. temperature, top_p, top_k and
+        seed: each a scalar for the whole batch or one value per
+        prompt."""
         self._adapter_indices(adapters, len(prompts))
+        samp = self._sampling(len(prompts), temperature, top_p, top_k,
+                              seed)
         with self._stream_ctx():
-            return self._generate_batch(prompts, max_new_tokens,
-                                        temperature, top_p,
+            return self._generate_batch(prompts, max_new_tokens, samp,
                                         adapters=adapters)
 
     def _adapter_indices(self, adapters, n: int):
@@ -608,22 +767,23 @@ class InferenceEngine:
         return [self._adapter_index(a) for a in adapters]
 
     @torch.no_grad()
-    def _generate_batch(self, prompts, max_new_tokens, temperature,
-                        top_p, budgets=None, adapters=None):
+    def _generate_batch(self, prompts, max_new_tokens, samp, budgets=None,
+                        adapters=None):
         outs = [[] for _ in prompts]
         for emitted in self._generate_batch_steps(
-                prompts, max_new_tokens, temperature, top_p, budgets,
-                adapters):
+                prompts, max_new_tokens, samp, budgets, adapters):
             for i, t in emitted:
                 outs[i].append(t)
         return outs
 
     def _batch_state(self, n, lmax, max_new_tokens, greedy):
         """Decode state for n prompts of at most lmax tokens: the
-        graphed MAX_BATCH-row decoder when the batch fits it (greedy, on
-        GPU), else eager state of exactly n rows."""
+        graphed MAX_BATCH-row decoder when the batch fits it (on GPU;
+        greedy batches only unless the engine samples on the device),
+        else eager state of exactly n rows."""
         cfg = self.model.cfg
-        if greedy and self.device.type == "cuda" and \
+        if (greedy or self.device_sampling) and \
+                self.device.type == "cuda" and \
                 n <= InferenceEngine.MAX_BATCH:
             cap = min(cfg.max_position_embeddings,
                       int(os.environ.get("DTX_SERVE_MAXS", "2048")))
@@ -639,11 +799,12 @@ class InferenceEngine:
                             self.device,
                             next(self.model.parameters()).dtype)
 
-    def _batch_prefill(self, st, prompts, aidx, temperature, top_p):
+    def _batch_prefill(self, st, prompts, aidx, samp):
         """Prefill every row into st's caches and hand the row lengths
-        over to its counters. Returns each row's first sampled token."""
+        over to its counters. Returns each row's first sampled token
+        (token 0 of its request)."""
         B, lens = len(prompts), [len(p) for p in prompts]
-        nxt = [0] * B
+        last = [None] * B           # each row's logits at its last token
         if B > 1 and self.device.type == "cuda":
             # ONE right-padded batched prefill (pads never attended:
             # causal + pads-after-real; len32 bounds decode reads)
@@ -655,8 +816,7 @@ class InferenceEngine:
             logits = self.model(padded, pos0=0, kv_caches=st.caches,
                                 **self._selection(aidx))
             for i in range(B):
-                nxt[i] = self._sample(logits[i, lens[i] - 1],
-                                      temperature, top_p)
+                last[i] = logits[i, lens[i] - 1]
         else:
             for i, ids in enumerate(prompts):
                 row = [c.row_view(i) for c in st.caches]
@@ -664,21 +824,32 @@ class InferenceEngine:
                                  device=self.device)
                 logits = self.model(t, pos0=0, kv_caches=row,
                                     **self._selection([aidx[i]]))
-                nxt[i] = self._sample(logits[0, -1], temperature, top_p)
+                last[i] = logits[0, -1]
+        if self.device_sampling:
+            # one call over the rows' last positions
+            nxt = self._device_sample(torch.stack(last), samp, 0).tolist()
+        else:
+            nxt = [self._host_sample(last[i], samp, i, 0)
+                   for i in range(B)]
         st.set_state(lens)
         return nxt
 
-    def _batch_step(self, st, cur, akw, temperature, top_p):
-        """One token for every row from the [B, 1] input `cur`: (tokens
-        on the host, the next step's input)."""
+    def _batch_step(self, st, cur, akw, samp, n):
+        """Token n of every row from the [B, 1] input `cur`: (tokens on
+        the host, the next step's input)."""
         if isinstance(st, _GraphedDecoder):
             st.step(cur)
             return st.out.tolist(), st.out.view(-1, 1)
         logits = self.model(cur, kv_caches=st.caches, pos_dev=st.pos32,
                             **akw)
+        if self.device_sampling:
+            from .. import ops
+            out = ops.sample(logits[:, -1], *st.sample_args())
+            st.advance()
+            return out.tolist(), out.view(-1, 1)
         st.advance()
-        if temperature and temperature > 0:
-            toks = [self._sample(logits[i, -1], temperature, top_p)
+        if not samp.greedy:
+            toks = [self._host_sample(logits[i, -1], samp, i, n)
                     for i in range(st.B)]
         else:
             toks = logits[:, -1].argmax(-1).tolist()
@@ -703,57 +874,63 @@ class InferenceEngine:
         return emitted
 
     @torch.no_grad()
-    def _generate_batch_steps(self, prompts, max_new_tokens, temperature,
-                              top_p, budgets=None, adapters=None):
+    def _generate_batch_steps(self, prompts, max_new_tokens, samp,
+                              budgets=None, adapters=None):
         """Yields, per decode step, the [(row, token)] emissions.
-        budgets: optional per-row max_tokens (rows stop emitting — and
-        count as done — at their own budget). adapters: optional
-        per-row adapter names."""
+        samp: the rows' _Sampling. budgets: optional per-row max_tokens
+        (rows stop emitting — and count as done — at their own budget).
+        adapters: optional per-row adapter names."""
         assert self.is_llama, "batched decode is the Llama path"
         aidx = self._adapter_indices(adapters, len(prompts))
         lens = [len(p) for p in prompts]
         if not prompts or min(lens) == 0:
             raise ValueError("empty prompt in batch")
         n_live = len(prompts)
-        st = self._batch_state(
-            n_live, max(lens), max_new_tokens,
-            greedy=not (temperature and temperature > 0))
-        # a graphed decoder has a fixed batch: pad with dummy rows on
-        # the base model
+        st = self._batch_state(n_live, max(lens), max_new_tokens,
+                               greedy=samp.greedy)
+        # a graphed decoder has a fixed batch: pad with greedy dummy
+        # rows on the base model
         prompts = list(prompts) + \
             [[self.tok.bos_token_id]] * (st.B - n_live)
         aidx = aidx + [-1] * (st.B - n_live)
+        samp = samp.padded(st.B)
         if isinstance(st, _GraphedDecoder):
             st.set_adapters(aidx)
+        st.set_sampling(samp)
         if budgets is None:
             budgets = [max_new_tokens] * n_live
         count, done = [0] * n_live, [False] * st.B
-        nxt = self._batch_prefill(st, prompts, aidx, temperature, top_p)
+        nxt = self._batch_prefill(st, prompts, aidx, samp)
         yield self._emit(nxt, done, count, budgets)
         cur = torch.tensor(nxt, dtype=torch.long,
                            device=self.device).view(-1, 1)
         akw = self._selection(aidx)
         cap = st.max_s - max(lens) - 2
-        for _ in range(min(max_new_tokens - 1, cap)):
+        for n in range(1, 1 + min(max_new_tokens - 1, cap)):
             if all(done[:n_live]):
                 break
-            toks, cur = self._batch_step(st, cur, akw, temperature, top_p)
+            toks, cur = self._batch_step(st, cur, akw, samp, n)
             yield self._emit(toks, done, count, budgets)
 
     def _encode_requests(self, requests):
+        """(prompts, budgets, _Sampling) of a batch of chat requests.
+        Requests with different sampling parameters share a batch only
+        where the engine samples on the device."""
         prompts = [self._encode_messages(r.get("messages", []))
                    for r in requests]
         budgets = [int(r.get("max_tokens", 64)) for r in requests]
-        temp = float(requests[0].get("temperature", 0.0))
-        top_p = float(requests[0].get("top_p", 1.0))
-        for r in requests[1:]:
-            if (float(r.get("temperature", 0.0)),
-                    float(r.get("top_p", 1.0))) != (temp, top_p):
-                # one batched generation samples with ONE setting; the
-                # BatchingFront groups requests by it before batching
-                raise ValueError("batched requests must share "
-                                 "temperature/top_p")
-        return prompts, budgets, temp, top_p
+        temps = [float(r.get("temperature", 0.0)) for r in requests]
+        top_ps = [float(r.get("top_p", 1.0)) for r in requests]
+        if not self.device_sampling and \
+                len(set(zip(temps, top_ps))) > 1:
+            # the host sampler draws a whole batch with ONE setting;
+            # the BatchingFront groups requests by it before batching
+            raise ValueError("batched requests must share "
+                             "temperature/top_p")
+        samp = self._sampling(len(requests), temps, top_ps,
+                              [r.get("top_k", 0) for r in requests],
+                              [r.get("seed") for r in requests])
+        return prompts, budgets, samp
 
     def _request_adapters(self, requests):
         """Per-request "adapter" names (None when no request names one);
@@ -765,15 +942,15 @@ class InferenceEngine:
         return names
 
     def chat_batch(self, requests: List[dict]) -> List[str]:
-        """requests: [{messages, max_tokens, temperature, top_p,
-        adapter}] -> completion texts (one batched generation; the
-        optional "adapter" is chosen per request)."""
-        prompts, budgets, temp, top_p = self._encode_requests(requests)
+        """requests: [{messages, max_tokens, temperature, top_p, top_k,
+        seed, adapter}] -> completion texts (one batched generation; the
+        optional "adapter", and on a device-sampling engine the sampling
+        parameters, are chosen per request)."""
+        prompts, budgets, samp = self._encode_requests(requests)
         names = self._request_adapters(requests)
         with self._stream_ctx():
-            outs = self._generate_batch(prompts, max(budgets), temp,
-                                        top_p, budgets=budgets,
-                                        adapters=names)
+            outs = self._generate_batch(prompts, max(budgets), samp,
+                                        budgets=budgets, adapters=names)
         return [self.tok.decode(o) for o in outs]
 
     def chat_batch_stream(self, requests: List[dict]):
@@ -781,14 +958,14 @@ class InferenceEngine:
         as tokens decode, then (row_index, None) when a row finishes.
         Deltas per row concatenate to exactly chat_batch()'s text (the
         same U+FFFD holdback as chat_stream)."""
-        prompts, budgets, temp, top_p = self._encode_requests(requests)
+        prompts, budgets, samp = self._encode_requests(requests)
         names = self._request_adapters(requests)
         n = len(requests)
         ids = [[] for _ in range(n)]
         sent = [""] * n
         with self._stream_ctx():
             for emitted in self._generate_batch_steps(
-                    prompts, max(budgets), temp, top_p, budgets=budgets,
+                    prompts, max(budgets), samp, budgets=budgets,
                     adapters=names):
                 for i, t in emitted:      # at most one token per row
                     ids[i].append(t)

@@ -64,9 +64,14 @@ class BatchingFront:
         t.start()
 
     @staticmethod
-    def _req(messages, max_tokens, temperature, top_p, adapter):
+    def _req(messages, max_tokens, temperature, top_p, adapter,
+             top_k=0, seed=None):
         req = {"messages": messages, "max_tokens": max_tokens,
                "temperature": temperature, "top_p": top_p}
+        if top_k:
+            req["top_k"] = top_k
+        if seed is not None:
+            req["seed"] = seed
         if adapter is not None:
             # multi-adapter serving: the adapter rides in the slot and
             # is chosen per row of the batch — requests for different
@@ -75,10 +80,10 @@ class BatchingFront:
         return req
 
     def chat(self, messages, max_tokens, temperature, top_p,
-             adapter=None):
+             adapter=None, top_k=0, seed=None):
         ev = threading.Event()
         slot = {"req": self._req(messages, max_tokens, temperature, top_p,
-                                 adapter),
+                                 adapter, top_k, seed),
                 "ev": ev}
         self._q.put(slot)
         ev.wait()
@@ -87,13 +92,13 @@ class BatchingFront:
         return slot["out"]
 
     def chat_stream(self, messages, max_tokens, temperature, top_p,
-                    adapter=None):
+                    adapter=None, top_k=0, seed=None):
         """Streamed request joining the batch: yields text deltas from
         a per-request queue fed by the worker (None = end)."""
         import queue
         tokq = queue.Queue()
         slot = {"req": self._req(messages, max_tokens, temperature, top_p,
-                                 adapter),
+                                 adapter, top_k, seed),
                 "tokq": tokq}
         self._q.put(slot)
         while True:
@@ -117,14 +122,18 @@ class BatchingFront:
                     batch.append(self._q.get(timeout=left))
                 except queue.Empty:
                     break
-            # requests only share a batched generation when their
-            # sampling params MATCH — the engine samples the whole
-            # batch with one (temperature, top_p), so a greedy request
-            # must never ride along with a sampled one
+            # an engine that samples on the device draws every row
+            # with its own parameters: the whole batch is one
+            # generation. Any other engine samples a batch with one
+            # (temperature, top_p), so requests only share a batched
+            # generation when those MATCH — a greedy request must never
+            # ride along with a sampled one
             groups = {}
+            mixed = getattr(self.engine, "device_sampling", False)
             for b in batch:
-                key = (float(b["req"].get("temperature", 0.0)),
-                       float(b["req"].get("top_p", 1.0)))
+                key = None if mixed else (
+                    float(b["req"].get("temperature", 0.0)),
+                    float(b["req"].get("top_p", 1.0)))
                 groups.setdefault(key, []).append(b)
             for batch in groups.values():
                 self._run_batch(batch)
@@ -139,8 +148,8 @@ class BatchingFront:
                 # single-stream (graphed) path instead
                 b = batch[0]
                 r = b["req"]
-                akw = ({"adapter": r["adapter"]} if "adapter" in r
-                       else {})
+                akw = {k: r[k] for k in ("adapter", "top_k", "seed")
+                       if k in r}
                 if "tokq" in b:
                     for d in self.engine.chat_stream(
                             r["messages"], r["max_tokens"],
@@ -214,6 +223,25 @@ def build_handler(pool, batcher=None, model_name: str = "datatunerx",
             return {"adapter": name}
         raise _UnknownModel(name)
 
+    def sampling_extras(body):
+        """kwargs for the engine call from the body's "top_k" (int,
+        default 0) and "seed" (int or null); absent ones are left out,
+        so an engine without them is called as before. Raises TypeError
+        or ValueError on malformed values."""
+        kw = {}
+        top_k, seed = body.get("top_k"), body.get("seed")
+        for name, v in (("top_k", top_k), ("seed", seed)):
+            if v is not None and (isinstance(v, bool) or
+                                  not isinstance(v, int)):
+                raise TypeError(f"{name} must be an integer")
+        if top_k is not None and top_k < 0:
+            raise ValueError("top_k must be >= 0")
+        if top_k:
+            kw["top_k"] = top_k
+        if seed is not None:
+            kw["seed"] = seed
+        return kw
+
     class _Lease:
         def __enter__(self):
             self.e = pool.acquire()
@@ -274,12 +302,15 @@ def build_handler(pool, batcher=None, model_name: str = "datatunerx",
                                 int(body.get("max_tokens", 64) or 64),
                                 float(body.get("temperature", 0.0) or 0),
                                 float(body.get("top_p", 1.0) or 1.0))
+                        skw = sampling_extras(body)
                     except (TypeError, ValueError):
                         self._send(400, {"error": "max_tokens/"
                                          "temperature/top_p must be "
-                                         "numbers"})
+                                         "numbers, top_k an integer "
+                                         ">= 0, seed an integer or "
+                                         "null"})
                         return
-                    akw = pick_adapter(body)
+                    akw = dict(pick_adapter(body), **skw)
                     if body.get("stream"):
                         # SSE token streaming (OpenAI chunk format)
                         self.send_response(200)
@@ -389,15 +420,18 @@ class TPFrontEngine:
         import torch.distributed as dist
         dist.broadcast_object_list([req], src=0)
 
-    def chat(self, messages, max_tokens, temperature, top_p):
+    def chat(self, messages, max_tokens, temperature, top_p, top_k=0,
+             seed=None):
         with self._mx:
             self._bcast({"op": "chat", "messages": messages,
                          "max_tokens": max_tokens,
-                         "temperature": temperature, "top_p": top_p})
+                         "temperature": temperature, "top_p": top_p,
+                         "top_k": top_k, "seed": seed})
             return self.engine.chat(messages, max_tokens, temperature,
-                                    top_p)
+                                    top_p, top_k=top_k, seed=seed)
 
-    def chat_stream(self, messages, max_tokens, temperature, top_p):
+    def chat_stream(self, messages, max_tokens, temperature, top_p,
+                    top_k=0, seed=None):
         # followers run the non-streaming chat(): token-identical loop,
         # so the TP collectives stay in lockstep with the streaming
         # front. The lock spans the DRAIN (this generator's body); the
@@ -405,9 +439,11 @@ class TPFrontEngine:
         with self._mx:
             self._bcast({"op": "chat", "messages": messages,
                          "max_tokens": max_tokens,
-                         "temperature": temperature, "top_p": top_p})
+                         "temperature": temperature, "top_p": top_p,
+                         "top_k": top_k, "seed": seed})
             yield from self.engine.chat_stream(messages, max_tokens,
-                                               temperature, top_p)
+                                               temperature, top_p,
+                                               top_k=top_k, seed=seed)
 
     def perplexity(self, texts):
         with self._mx:
@@ -430,7 +466,8 @@ def tp_follower_loop(engine):
         req = obj[0]
         if req["op"] == "chat":
             engine.chat(req["messages"], req["max_tokens"],
-                        req["temperature"], req["top_p"])
+                        req["temperature"], req["top_p"],
+                        top_k=req.get("top_k", 0), seed=req.get("seed"))
         elif req["op"] == "ppl":
             engine.perplexity(req["texts"])
         elif req["op"] == "chat_batch":

@@ -11,6 +11,11 @@ multi-adapter mode with N stacked adapters, row i of the batch using
 adapter i mod N; `--compare-adapters` runs single / multi 1 / multi 8 in
 one process, alternating, for the chosen --quantization.
 
+Sampling: `--temperature T` (with `--top-p`, `--top-k`) samples every
+row instead of taking the argmax; `--mixed` alternates greedy and
+sampled rows in one batch (rows 0, 2, ... greedy), which needs an
+engine that samples on the device. Seeds are fixed (row i: seed i).
+
 Run on the GPU box: python tools/bench_decode.py [--no-graph]
 """
 
@@ -79,10 +84,25 @@ def build(dev, quantization, graph, adapters=0):
                            graph_decode=graph)
 
 
-def run(eng, tokens, batch):
+def sampling_kwargs(args, batch):
+    """generate / generate_batch keywords for the sampling flags ({}:
+    greedy, the calls as they always were)."""
+    if not args.temperature > 0:
+        return {}
+    if batch == 1:
+        return {"temperature": args.temperature, "top_p": args.top_p,
+                "top_k": args.top_k, "seed": 0}
+    temps = [0.0 if args.mixed and i % 2 == 0 else args.temperature
+             for i in range(batch)]
+    return {"temperature": temps, "top_p": args.top_p,
+            "top_k": args.top_k, "seed": list(range(batch))}
+
+
+def run(eng, tokens, batch, skw=None):
     """One timed generation; returns decoded tokens per second (all
     rows). Random weights never emit a stop token reliably, so count
-    what was actually produced."""
+    what was actually produced. skw: sampling_kwargs()."""
+    skw = skw or {}
     prompt = list(range(5, 5 + 96))
     reg = getattr(eng.model, "adapters", None)
     names = ([reg.names[i % len(reg)] for i in range(batch)]
@@ -90,12 +110,12 @@ def run(eng, tokens, batch):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     if batch > 1:
-        kw = {"adapters": names} if names else {}
+        kw = dict(skw, **({"adapters": names} if names else {}))
         outs = eng.generate_batch([prompt] * batch, max_new_tokens=tokens,
                                   **kw)
         n = sum(len(o) for o in outs)
     else:
-        kw = {"adapter": names[0]} if names else {}
+        kw = dict(skw, **({"adapter": names[0]} if names else {}))
         n = len(eng.generate(prompt, max_new_tokens=tokens, **kw))
     torch.cuda.synchronize()
     return n / (time.perf_counter() - t0), n
@@ -116,7 +136,17 @@ def main():
                     help="one adapter served the single-adapter way")
     ap.add_argument("--compare-adapters", action="store_true",
                     help="single adapter / multi 1 / multi 8, interleaved")
+    ap.add_argument("--temperature", type=float, default=0.0,
+                    help="sample every row at this temperature (0: greedy)")
+    ap.add_argument("--top-p", type=float, default=1.0)
+    ap.add_argument("--top-k", type=int, default=0)
+    ap.add_argument("--mixed", action="store_true",
+                    help="rows alternate greedy and sampled (needs "
+                         "--temperature and --batch > 1)")
     args = ap.parse_args()
+    if args.mixed and not (args.temperature > 0 and args.batch > 1):
+        ap.error("--mixed needs --temperature > 0 and --batch > 1")
+    skw = sampling_kwargs(args, args.batch)
     dev = torch.device("cuda")
     if args.compare_adapters:
         compare_adapters(args, dev)
@@ -132,18 +162,19 @@ def main():
         # memory of this arm alone: relative to what earlier arms hold
         base = torch.cuda.memory_allocated()
         engines[q] = build(dev, q, not args.no_graph, adapters)
-        run(engines[q], 8, args.batch)     # warmup (captures the graph)
+        run(engines[q], 8, args.batch, skw)    # warmup (captures the graph)
         mem[q] = (torch.cuda.memory_allocated() - base,
                   torch.cuda.max_memory_allocated() - base)
     rates = {q: [] for q in arms}
     for _ in range(args.reps):
         for q in arms:                     # arms alternate per repetition
-            rates[q].append(run(engines[q], args.tokens, args.batch))
+            rates[q].append(run(engines[q], args.tokens, args.batch, skw))
     for q in arms:
         tps = statistics.median(r for r, _ in rates[q])
         n = rates[q][0][1]
+        mode = ("mixed " if args.mixed else "sampled ") if skw else ""
         print(f"{q or 'bf16'} graph={not args.no_graph} "
-              f"batch={args.batch}: {n} tokens, {tps:.1f} tok/s "
+              f"{mode}batch={args.batch}: {n} tokens, {tps:.1f} tok/s "
               f"(min {min(r for r, _ in rates[q]):.1f}, "
               f"max {max(r for r, _ in rates[q]):.1f}); allocated "
               f"{mem[q][0] / 2**30:.2f} GiB steady, "
