@@ -2,6 +2,7 @@
 // param write) + deterministic two-stage L2 norm.
 // Matches torch.optim.AdamW semantics (ops/reference.py adamw_step).
 #include "dtx_common.h"
+#include "dtx_launch.h"
 
 // p_out: params in their own dtype (bf16 on GPU; f32 master is
 // authoritative). grad fp32 (trainer accumulates micro-batch grads fp32).

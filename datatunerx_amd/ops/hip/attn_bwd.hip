@@ -31,6 +31,7 @@
 //
 // Numerics contract: ops/reference.py attn_bwd.
 #include "dtx_mfma.h"
+#include "dtx_launch.h"
 
 // ------------------------------------------------------------- dk/dv
 // 8 waves (512 threads), TWO waves per SIMD: waves 0-3 accumulate dV

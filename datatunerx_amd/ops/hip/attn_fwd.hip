@@ -32,6 +32,7 @@
 // the wave's first document are skipped, boundary tiles add kv < doc_start
 // to the causal select. DOCS = false compiles to the plain causal kernel.
 #include "dtx_mfma.h"
+#include "dtx_launch.h"
 
 template <int D>
 struct AttnFwdLds {

@@ -1,115 +1,115 @@
-// Torch bindings for the gfx950 HIP kernel library.
-// All tensors must be contiguous; bf16 compute dtype, fp32 reductions.
+// Torch bindings for the gfx950 HIP kernel library. The kernels index their
+// pointers unchecked, so these bindings are the single gate: every pointer
+// a kernel dereferences is checked here for device, dtype, density and
+// element count (docs/kernels.md, "Binding contract"); dtx_launch.h says
+// what each launcher assumes. bf16 compute dtype, fp32 reductions.
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
 #include <hip/hip_runtime.h>
+#include <climits>
 
-// ---- launchers (defined in the .hip files) ----
-void launch_rmsnorm_fwd(const void*, const void*, void*, float*, int, int,
-                        float, hipStream_t);
-int rmsnorm_bwd_nblocks(int M);
-void launch_rmsnorm_bwd(const void*, const void*, const void*, const float*,
-                        const void*, void*, float*, float*, int, int,
-                        hipStream_t);
-void launch_rope(const void*, const float*, const float*, void*, long, int,
-                 int, int, int, int, const int*, int, const int*,
-                 hipStream_t);
-void launch_swiglu_fwd(const void*, const void*, void*, long, hipStream_t);
-void launch_swiglu_bwd(const void*, const void*, const void*, void*, void*,
-                       long, hipStream_t);
-void launch_xent_fwd(const void*, const long*, float*, float*, long, int,
-                     long, hipStream_t);
-void launch_xent_bwd(const void*, const long*, const float*, const float*,
-                     void*, long, int, long, hipStream_t);
-void launch_dequant_int8(const void*, const float*, void*, long, int,
-                         hipStream_t);
-void launch_dequant_int4(const void*, const float*, void*, long, int, int,
-                         hipStream_t);
-void launch_xent_lse_merge(const void*, const long*, float*, float*,
-                           float*, long, int, long, long, hipStream_t);
-void launch_xent_dlogits(const void*, const long*, const float*, void*,
-                         long, int, long, long, hipStream_t);
-void launch_adamw(void*, float*, const float*, float*, float*, long, float,
-                  float, float, float, float, int, hipStream_t);
-void launch_l2_norm(const float*, float*, float*, long, hipStream_t);
-int lora_contract_ksplit(int K, long M, int r);
-void launch_dropout_mask(void*, long, unsigned long long, float,
-                         hipStream_t);
-void launch_lora_contract(const void*, const void*, const void*, float*,
-                          float*, long, int, int, unsigned long long,
-                          float, hipStream_t);
-void launch_lora_expand_add(void*, const float*, const void*, const void*,
-                            long, int, int, float, unsigned long long,
-                            float, hipStream_t);
-bool lora_expand_rng_ok(long M, int N, int r);
-int lora_wgrad_splitm(int K, int r, long M);
-void launch_lora_contract2(const void*, const void*, const void*, float*,
-                           float*, long, int, int, unsigned long long,
-                           unsigned long long, float, hipStream_t);
-void launch_lora_expand_add_dual(void*, const float*, const float*,
-                                 const void*, const void*, long, int, int,
-                                 float, unsigned long long,
-                                 unsigned long long, float, hipStream_t);
-void launch_lora_wgrad(const float*, const void*, const void*, float*,
-                       float*, long, int, int, float, unsigned long long,
-                       float, hipStream_t);
-void launch_attn_fwd(const void*, const void*, const void*, void*, float*,
-                     const int*, int, int, int, int, int, int, float, int,
-                     hipStream_t);
-void launch_transpose_sd(const void*, void*, int, int, int, int,
-                         hipStream_t);
-int attn_decode_nsplit(int Skv);
-void launch_gemv_bf16(const void*, const void*, void*, int, int,
-                      hipStream_t);
-void launch_qgemv_int8(const void*, const void*, const float*, void*, int,
-                       int, int, hipStream_t);
-void launch_qgemv_int4(const void*, const void*, const float*, void*, int,
-                       int, int, int, hipStream_t);
-void launch_mlora_shrink(const void*, const void*, const int*, float*, int,
-                         int, int, int, hipStream_t);
-void launch_mlora_expand_add(void*, const float*, const void*, const float*,
-                             const int*, int, int, int, int, hipStream_t);
-void launch_gemm_nt(const void*, const void*, const void*, void*, long,
-                    int, int, hipStream_t);
-long sample_max_vocab();
-void launch_sample(const void*, long, int, int, const float*, const float*,
-                   const int*, const long long*, const int*, const float*,
-                   long long*, hipStream_t);
-void launch_attn_decode(const void*, const void*, const void*,
-                        const int*, float*, void*, float*, int, int, int,
-                        int, int, float, int, hipStream_t);
-void launch_attn_bwd_dkdv(const void*, const void*, const void*,
-                          const void*, const float*, const float*,
-                          void*, void*, const int*, int, int, int, int,
-                          int, int, float, int, hipStream_t);
-void launch_attn_bwd_dq(const void*, const void*, const void*,
-                        const void*, const void*, const float*, float*,
-                        void*, const int*, int, int, int, int, int, int,
-                        float, int, hipStream_t);
+#include "dtx_launch.h"
 
 namespace {
 
-hipStream_t cur_stream() {
-  return (hipStream_t)at::cuda::getCurrentCUDAStream().stream();
+using torch::Tensor;
+using OptTensor = c10::optional<torch::Tensor>;
+constexpr auto BF16 = torch::kBFloat16;
+constexpr auto F32 = torch::kFloat;
+constexpr auto I32 = torch::kInt;
+constexpr auto I64 = torch::kLong;
+
+// A size on its way to an int parameter of a launcher.
+static int i32(long v) {
+  TORCH_CHECK(v >= INT_MIN && v <= INT_MAX, "size ", v, " exceeds int");
+  return (int)v;
 }
 
-void check_bf16_contig(const torch::Tensor& t, const char* name) {
-  TORCH_CHECK(t.is_cuda(), name, " must be on GPU");
-  TORCH_CHECK(t.scalar_type() == torch::kBFloat16, name, " must be bf16");
-  TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
+const char* dt_name(at::ScalarType ty) {
+  switch (ty) {
+    case at::kBFloat16: return "bf16";
+    case at::kFloat: return "f32";
+    case at::kInt: return "int32";
+    case at::kLong: return "int64";
+    case at::kChar: return "int8";
+    default: return c10::toString(ty);
+  }
 }
 
-// Sequence-packing maps (doc_start / doc_end): int32 [B,S] on the GPU.
-// The kernels index them unchecked, so shape and layout are pinned here.
-const int* doc_map_ptr(const c10::optional<torch::Tensor>& t, long B,
-                       long S, const char* name) {
-  if (!t.has_value()) return nullptr;
-  TORCH_CHECK(t->is_cuda(), name, " must be on GPU");
-  TORCH_CHECK(t->scalar_type() == torch::kInt, name, " must be int32");
-  TORCH_CHECK(t->dim() == 2 && t->size(0) == B && t->size(1) == S, name,
-              " must be [B,S]");
-  TORCH_CHECK(t->is_contiguous(), name, " must be contiguous");
-  return t->data_ptr<int>();
+// The check vocabulary. A binding opens with one Op over its first tensor
+// and passes every other tensor through dev / dense / opt before it takes
+// a data_ptr; these are the only places that look at a tensor's device,
+// dtype and layout.
+struct Op {
+  const char* op;
+  const Tensor& ref;
+  hipStream_t stream;   // the current device's current stream
+
+  // The first tensor pins the device: the launch goes to the CURRENT
+  // device's stream; another GPU's tensor is refused, not followed. This
+  // form checks the device alone (dropout_mask's `like`).
+  Op(const char* op_, const Tensor& first, const char* name)
+      : op(op_), ref(first) {
+    TORCH_CHECK(first.is_cuda(), op, ": ", name, " must be on the GPU");
+    const auto cur = at::cuda::getCurrentCUDAStream();
+    stream = (hipStream_t)cur.stream();
+    TORCH_CHECK(first.get_device() == cur.device_index(), op, ": ", name,
+                " must be on the current GPU");
+  }
+  Op(const char* op_, const Tensor& first, at::ScalarType ty,
+     const char* name, bool contiguous = true) : Op(op_, first, name) {
+    contiguous ? dense(first, ty, name) : dev(first, ty, name);
+  }
+  // on the GPU of the first tensor, of dtype ty (any strides)
+  const Tensor& dev(const Tensor& t, at::ScalarType ty,
+                    const char* name) const {
+    TORCH_CHECK(t.is_cuda() && t.get_device() == ref.get_device() &&
+                t.scalar_type() == ty, op, ": ", name, " must be ",
+                dt_name(ty), " on the GPU of the first argument");
+    return t;
+  }
+  // dev + contiguous (+ exactly n elements)
+  const Tensor& dense(const Tensor& t, at::ScalarType ty, const char* name,
+                      long n = -1) const {
+    TORCH_CHECK(dev(t, ty, name).is_contiguous(), op, ": ", name,
+                " must be contiguous");
+    TORCH_CHECK(n < 0 || t.numel() == n, op, ": ", name, " must be ", n,
+                " elements long, got ", t.numel());
+    return t;
+  }
+  void shape(const Tensor& t, at::IntArrayRef want, const char* name) const {
+    TORCH_CHECK(t.sizes() == want, op, ": ", name, " must be ", want,
+                ", got ", t.sizes());
+  }
+  // optional dense tensor: its pointer, or nullptr
+  template <typename T = void>
+  const T* opt(const OptTensor& t, at::ScalarType ty, const char* name,
+               long n = -1) const {
+    if (!t.has_value()) return nullptr;
+    return static_cast<const T*>(dense(*t, ty, name, n).data_ptr());
+  }
+  // for the tensors a kernel reads or writes in 16-byte pieces
+  void aligned16(const char* names,
+                 std::initializer_list<const void*> ptrs) const {
+    for (const void* p : ptrs)
+      TORCH_CHECK((uintptr_t)p % 16 == 0, op, ": ", names,
+                  " need 16-byte alignment");
+  }
+  // M of x [..., inner] (inner < 0: x's own last dimension, not empty)
+  long rows(const Tensor& x, const char* name, long inner = -1) const {
+    TORCH_CHECK(x.dim() >= 1 && x.size(-1) > 0, op, ": ", name,
+                " must be [..., n] with n > 0");
+    TORCH_CHECK(inner < 0 || x.size(-1) == inner, op, ": ", name,
+                " must be [..., ", inner, "], got ", x.sizes());
+    return x.numel() / x.size(-1);
+  }
+};
+
+// Sequence-packing maps (doc_start / doc_end): int32 [B,S].
+const int* doc_map(const Op& op, const OptTensor& t, long B, long S,
+                   const char* name) {
+  if (t.has_value()) op.shape(*t, {B, S}, name);
+  return op.opt<int>(t, I32, name);
 }
 
 // doc_start needs the training shape: causal self-attention over S > 1.
@@ -124,508 +124,534 @@ void check_docs_shape(bool causal, long S, long Skv) {
 // thread: H <= 8 * 8 * 256. A wider row would lose its tail silently.
 constexpr long RMSNORM_MAX_H = 8L * 8 * 256;
 
-void check_rmsnorm_row(const torch::Tensor& x, const torch::Tensor& w) {
-  check_bf16_contig(x, "x");
-  check_bf16_contig(w, "w");
-  TORCH_CHECK(x.dim() >= 1 && x.size(-1) > 0, "x must be [..., H]");
-  const long H = x.size(-1);
-  TORCH_CHECK(H % 8 == 0, "H % 8");
+// x [M,H], w [H]: M
+static long rmsnorm_rows(const Op& op, const Tensor& x, const Tensor& w) {
+  const long M = op.rows(x, "x"), H = x.size(-1);
+  TORCH_CHECK(H % 8 == 0, op.op, ": H % 8");
   TORCH_CHECK(H <= RMSNORM_MAX_H, "rmsnorm: H = ", H,
               " is above the kernel limit of ", RMSNORM_MAX_H);
-  TORCH_CHECK(w.numel() == H, "w must have H elements");
+  op.dense(w, BF16, "w", H);
+  op.aligned16("x, w", {x.data_ptr(), w.data_ptr()});
+  return M;
 }
 
-std::vector<torch::Tensor> rmsnorm_fwd(torch::Tensor x, torch::Tensor w,
-                                       double eps) {
-  check_rmsnorm_row(x, w);
-  const int H = (int)x.size(-1);
-  const long M = x.numel() / H;
+std::vector<Tensor> rmsnorm_fwd(Tensor x, Tensor w, double eps) {
+  const Op op("rmsnorm_fwd", x, BF16, "x");
+  const int M = i32(rmsnorm_rows(op, x, w)), H = i32(x.size(-1));
   auto y = torch::empty_like(x);
-  auto inv = torch::empty({M}, x.options().dtype(torch::kFloat));
+  auto inv = torch::empty({M}, x.options().dtype(F32));
+  if (M == 0) return {y, inv};
   launch_rmsnorm_fwd(x.data_ptr(), w.data_ptr(), y.data_ptr(),
-                     inv.data_ptr<float>(), (int)M, H, (float)eps,
-                     cur_stream());
+                     inv.data_ptr<float>(), M, H, (float)eps, op.stream);
   return {y, inv};
 }
 
-std::vector<torch::Tensor> rmsnorm_bwd(torch::Tensor dy, torch::Tensor x,
-                                       torch::Tensor w, torch::Tensor inv,
-                                       c10::optional<torch::Tensor> dres) {
-  check_bf16_contig(dy, "dy");
-  check_rmsnorm_row(x, w);
-  const int H = (int)x.size(-1);
-  const long M = x.numel() / H;
-  TORCH_CHECK(dy.sizes() == x.sizes(), "dy must have the shape of x");
-  TORCH_CHECK(inv.is_cuda() && inv.scalar_type() == torch::kFloat &&
-              inv.is_contiguous() && inv.numel() == M,
-              "inv must be contiguous f32 on GPU with one element per row");
+std::vector<Tensor> rmsnorm_bwd(Tensor dy, Tensor x, Tensor w, Tensor inv,
+                                OptTensor dres) {
+  const Op op("rmsnorm_bwd", dy, BF16, "dy");
+  op.dense(x, BF16, "x");
+  const int M = i32(rmsnorm_rows(op, x, w)), H = i32(x.size(-1));
+  op.shape(dy, x.sizes(), "dy");
+  op.dense(inv, F32, "inv", M);
+  const void* drp = op.opt(dres, BF16, "dres", x.numel());
+  op.aligned16("dy, dres", {dy.data_ptr(), drp});
   auto dx = torch::empty_like(x);
-  auto dw = torch::empty({H}, x.options().dtype(torch::kFloat));
-  const int nb = rmsnorm_bwd_nblocks((int)M);
-  auto part = torch::empty({nb, H}, x.options().dtype(torch::kFloat));
-  const void* drp = nullptr;
-  if (dres.has_value()) {
-    check_bf16_contig(*dres, "dres");
-    TORCH_CHECK(dres->numel() == x.numel(), "dres shape");
-    drp = dres->data_ptr();
-  }
+  if (M == 0) return {dx, torch::zeros({H}, x.options().dtype(F32))};
+  auto dw = torch::empty({H}, x.options().dtype(F32));
+  auto part = torch::empty({rmsnorm_bwd_nblocks(M), H}, dw.options());
   launch_rmsnorm_bwd(dy.data_ptr(), x.data_ptr(), w.data_ptr(),
                      inv.data_ptr<float>(), drp, dx.data_ptr(),
-                     part.data_ptr<float>(), dw.data_ptr<float>(), (int)M, H,
-                     cur_stream());
+                     part.data_ptr<float>(), dw.data_ptr<float>(), M, H,
+                     op.stream);
   return {dx, dw};
 }
 
 // ---------------------------------------------------------------- RoPE
-torch::Tensor rope(torch::Tensor x, torch::Tensor cosb, torch::Tensor sinb,
-                   long pos0, bool backward,
-                   c10::optional<torch::Tensor> pos_dev,
-                   c10::optional<torch::Tensor> doc_start) {
-  check_bf16_contig(x, "x");
-  TORCH_CHECK(x.dim() == 4, "x must be [B,S,H,D]");
-  TORCH_CHECK(cosb.scalar_type() == torch::kFloat && cosb.is_contiguous());
-  const int B = (int)x.size(0), S = (int)x.size(1), H = (int)x.size(2),
-            D = (int)x.size(3);
-  TORCH_CHECK(D % 8 == 0, "D % 8");
-  const int* dsp = doc_map_ptr(doc_start, B, S, "doc_start");
+// The values inside pos_dev are the caller's contract (dtx_launch.h).
+Tensor rope(Tensor x, Tensor cosb, Tensor sinb, long pos0, bool backward,
+            OptTensor pos_dev, OptTensor doc_start) {
+  const Op op("rope", x, BF16, "x");
+  TORCH_CHECK(x.dim() == 4, "rope: x must be [B,S,H,D]");
+  const long B = x.size(0);
+  const int S = i32(x.size(1)), H = i32(x.size(2)), D = i32(x.size(3));
+  TORCH_CHECK(D % 8 == 0, "rope: D % 8");
+  TORCH_CHECK(pos0 >= 0, "rope: pos0 must be >= 0");
+  op.dense(cosb, F32, "cosb");
+  TORCH_CHECK(cosb.dim() == 2 && cosb.size(1) == D / 2,
+              "rope: cosb must be [rows, D/2]");
+  op.shape(op.dense(sinb, F32, "sinb"), cosb.sizes(), "sinb");
+  op.aligned16("cosb, sinb", {cosb.data_ptr(), sinb.data_ptr()});
+  const int* dsp = doc_map(op, doc_start, B, S, "doc_start");
   TORCH_CHECK(!(dsp && pos_dev.has_value()),
               "doc_start cannot be combined with pos_dev");
-  const int* pd = nullptr;
-  int pos_per_b = 0;
-  if (pos_dev.has_value()) {
-    TORCH_CHECK(pos_dev->scalar_type() == torch::kInt &&
-                pos_dev->is_cuda(), "pos_dev must be int32 on GPU");
-    pd = pos_dev->data_ptr<int>();
-    pos_per_b = pos_dev->numel() > 1;
-    if (pos_per_b)
-      TORCH_CHECK(pos_dev->numel() == B, "pos_dev must be [1] or [B]");
-    TORCH_CHECK(cosb.size(0) >= S, "rope table too short");
-  } else {
-    TORCH_CHECK(cosb.size(0) >= pos0 + S, "rope table too short");
-  }
+  const int* pd = op.opt<int>(pos_dev, I32, "pos_dev");
+  TORCH_CHECK(!pd || pos_dev->numel() == 1 || pos_dev->numel() == B,
+              "rope: pos_dev must be [1] or [B]");
+  const int pos_per_b = pd && pos_dev->numel() > 1;
+  TORCH_CHECK(cosb.size(0) >= (pd ? S : pos0 + S), "rope table too short");
   auto y = torch::empty_like(x);
+  if (x.numel() == 0) return y;
   launch_rope(x.data_ptr(), cosb.data_ptr<float>(), sinb.data_ptr<float>(),
-              y.data_ptr(), B, S, H, D, (int)pos0, backward ? 1 : 0, pd,
-              pos_per_b, dsp, cur_stream());
+              y.data_ptr(), B, S, H, D, i32(pos0), backward ? 1 : 0, pd,
+              pos_per_b, dsp, op.stream);
   return y;
 }
 
 // --------------------------------------------------------------- SwiGLU
-torch::Tensor swiglu_fwd(torch::Tensor gate, torch::Tensor up) {
-  check_bf16_contig(gate, "gate");
-  check_bf16_contig(up, "up");
-  TORCH_CHECK(gate.numel() % 8 == 0);
+Tensor swiglu_fwd(Tensor gate, Tensor up) {
+  const Op op("swiglu_fwd", gate, BF16, "gate");
+  op.shape(op.dense(up, BF16, "up"), gate.sizes(), "up");
+  TORCH_CHECK(gate.numel() % 8 == 0, "swiglu_fwd: numel % 8");
+  op.aligned16("gate, up", {gate.data_ptr(), up.data_ptr()});
   auto out = torch::empty_like(gate);
+  if (gate.numel() == 0) return out;
   launch_swiglu_fwd(gate.data_ptr(), up.data_ptr(), out.data_ptr(),
-                    gate.numel(), cur_stream());
+                    gate.numel(), op.stream);
   return out;
 }
 
-std::vector<torch::Tensor> swiglu_bwd(torch::Tensor dout, torch::Tensor gate,
-                                      torch::Tensor up) {
-  check_bf16_contig(dout, "dout");
-  check_bf16_contig(gate, "gate");
-  check_bf16_contig(up, "up");
-  TORCH_CHECK(gate.numel() % 8 == 0);
-  TORCH_CHECK(up.sizes() == gate.sizes() && dout.sizes() == gate.sizes(),
-              "dout, gate and up must have one shape");
+std::vector<Tensor> swiglu_bwd(Tensor dout, Tensor gate, Tensor up) {
+  const Op op("swiglu_bwd", dout, BF16, "dout");
+  op.shape(op.dense(gate, BF16, "gate"), dout.sizes(), "gate");
+  op.shape(op.dense(up, BF16, "up"), dout.sizes(), "up");
+  TORCH_CHECK(gate.numel() % 8 == 0, "swiglu_bwd: numel % 8");
+  op.aligned16("dout, gate, up",
+               {dout.data_ptr(), gate.data_ptr(), up.data_ptr()});
   auto dg = torch::empty_like(gate);
   auto du = torch::empty_like(up);
+  if (gate.numel() == 0) return {dg, du};
   launch_swiglu_bwd(dout.data_ptr(), gate.data_ptr(), up.data_ptr(),
                     dg.data_ptr(), du.data_ptr(), gate.numel(),
-                    cur_stream());
+                    op.stream);
   return {dg, du};
 }
 
 // -------------------------------------------------------- cross entropy
-std::vector<torch::Tensor> xent_fwd(torch::Tensor logits,
-                                    torch::Tensor targets, long ignore) {
-  check_bf16_contig(logits, "logits");
-  TORCH_CHECK(targets.scalar_type() == torch::kLong);
-  const int V = (int)logits.size(-1);
-  const long N = logits.numel() / V;
-  TORCH_CHECK(V % 8 == 0, "V % 8");
-  auto loss = torch::empty({N}, logits.options().dtype(torch::kFloat));
-  auto lse = torch::empty({N}, logits.options().dtype(torch::kFloat));
+// logits [N,V] in whole 16-byte groups, targets [N] int64: N. Target
+// VALUES are not inspected (that would be a host sync): caller's contract.
+static long xent_rows(const Op& op, const Tensor& logits, const Tensor& tg) {
+  const long N = op.rows(logits, "logits");
+  TORCH_CHECK(logits.size(-1) % 8 == 0, op.op, ": V % 8");
+  op.aligned16("logits", {logits.data_ptr()});
+  op.dense(tg, I64, "targets", N);
+  return N;
+}
+
+std::vector<Tensor> xent_fwd(Tensor logits, Tensor targets, long ignore) {
+  const Op op("xent_fwd", logits, BF16, "logits");
+  const long N = xent_rows(op, logits, targets);
+  const int V = i32(logits.size(-1));
+  auto loss = torch::empty({N}, logits.options().dtype(F32));
+  auto lse = torch::empty_like(loss);
+  if (N == 0) return {loss, lse};
   launch_xent_fwd(logits.data_ptr(), targets.data_ptr<long>(),
                   loss.data_ptr<float>(), lse.data_ptr<float>(), N, V,
-                  ignore, cur_stream());
+                  ignore, op.stream);
   return {loss, lse};
 }
 
-torch::Tensor xent_bwd(torch::Tensor logits, torch::Tensor targets,
-                       torch::Tensor lse, torch::Tensor dloss, long ignore) {
-  check_bf16_contig(logits, "logits");
-  const int V = (int)logits.size(-1);
-  const long N = logits.numel() / V;
+Tensor xent_bwd(Tensor logits, Tensor targets, Tensor lse, Tensor dloss,
+                long ignore) {
+  const Op op("xent_bwd", logits, BF16, "logits");
+  const long N = xent_rows(op, logits, targets);
+  const int V = i32(logits.size(-1));
+  op.dense(lse, F32, "lse", N);
+  op.dense(dloss, F32, "dloss", N);
   auto dlogits = torch::empty_like(logits);
+  if (N == 0) return dlogits;
   launch_xent_bwd(logits.data_ptr(), targets.data_ptr<long>(),
                   lse.data_ptr<float>(), dloss.data_ptr<float>(),
-                  dlogits.data_ptr(), N, V, ignore, cur_stream());
+                  dlogits.data_ptr(), N, V, ignore, op.stream);
   return dlogits;
 }
 
-// ----------------------------------------------------------------- LoRA
-// Optional `mask` (bf16, same shape as x / y) fuses the PEFT-style
-// input dropout into the kernels (no mask-multiply materialization).
-static const void* opt_mask(const c10::optional<torch::Tensor>& m,
-                            long numel, const char* name) {
-  if (!m.has_value()) return nullptr;
-  check_bf16_contig(*m, name);
-  TORCH_CHECK(m->numel() == numel, name, " shape mismatch");
-  return m->data_ptr();
+// chunked-vocab CE: online LSE merge over one logits chunk (in-place
+// m/l/tgt update) and the per-chunk dlogits for the dX sweep.
+void xent_lse_merge(Tensor logits, Tensor targets, Tensor m_run,
+                    Tensor l_run, Tensor tgt, long v0, long ignore_index) {
+  const Op op("xent_lse_merge", logits, BF16, "logits");
+  const long N = xent_rows(op, logits, targets);
+  const int Vc = i32(logits.size(-1));
+  TORCH_CHECK(v0 >= 0, "xent_lse_merge: v0 must be >= 0");
+  op.dense(m_run, F32, "m_run", N);
+  op.dense(l_run, F32, "l_run", N);
+  op.dense(tgt, F32, "tgt", N);
+  if (N == 0) return;
+  launch_xent_lse_merge(logits.data_ptr(), targets.data_ptr<long>(),
+                        m_run.data_ptr<float>(), l_run.data_ptr<float>(),
+                        tgt.data_ptr<float>(), N, Vc, v0, ignore_index,
+                        op.stream);
 }
 
-torch::Tensor lora_contract(torch::Tensor x, torch::Tensor w,
-                            c10::optional<torch::Tensor> mask,
-                            int64_t seed, double keep) {
-  check_bf16_contig(x, "x");
-  check_bf16_contig(w, "w");
-  const int K = (int)x.size(-1);
-  const long M = x.numel() / K;
-  const int r = (int)w.size(0);
-  TORCH_CHECK(w.size(1) == K, "w [r,K] mismatch");
-  TORCH_CHECK(r <= 64, "r <= 64");
-  TORCH_CHECK(K % 8 == 0);
-  auto t = torch::empty({M, r}, x.options().dtype(torch::kFloat));
+Tensor xent_dlogits(Tensor logits, Tensor targets, Tensor lse, long v0,
+                    long ignore_index) {
+  const Op op("xent_dlogits", logits, BF16, "logits");
+  const long N = xent_rows(op, logits, targets);
+  const int Vc = i32(logits.size(-1));
+  TORCH_CHECK(v0 >= 0, "xent_dlogits: v0 must be >= 0");
+  op.dense(lse, F32, "lse", N);
+  auto dl = torch::empty_like(logits);
+  if (N == 0) return dl;
+  launch_xent_dlogits(logits.data_ptr(), targets.data_ptr<long>(),
+                      lse.data_ptr<float>(), dl.data_ptr(), N, Vc, v0,
+                      ignore_index, op.stream);
+  return dl;
+}
+
+// ----------------------------------------------------------------- LoRA
+// Dropout enters as an optional `mask` (bf16, same shape as x / y; no
+// mask-multiply materialization) or as seed + keep < 1 (in-kernel RNG).
+// The kernels read the rows of x, y and of the adapters [r, inner] in
+// 16-byte pieces: inner % 8, aligned bases.
+
+// x or y [M, inner]: M
+static long lora_rows(const Op& op, const Tensor& x, const char* name) {
+  const long M = op.rows(x, name);
+  TORCH_CHECK(x.size(-1) % 8 == 0, op.op, ": ", name, " width % 8");
+  op.aligned16(name, {x.data_ptr()});
+  return M;
+}
+
+// adapter [r, inner] with r >= 1, and r <= rmax where rmax > 0: r
+static int lora_rank(const Op& op, const Tensor& w, const char* name,
+                     long inner, long rmax = 0) {
+  op.dense(w, BF16, name);
+  TORCH_CHECK(w.dim() == 2 && w.size(1) == inner && w.size(0) >= 1, op.op,
+              ": ", name, " must be [r,", inner, "] with r >= 1, got ",
+              w.sizes());
+  TORCH_CHECK(rmax <= 0 || w.size(0) <= rmax, op.op, ": r <= ", rmax,
+              ", got ", name, " ", w.sizes());
+  op.aligned16(name, {w.data_ptr()});
+  return i32(w.size(0));
+}
+
+void check_keep(const Op& op, double keep) {
+  TORCH_CHECK(keep > 0.0 && keep <= 1.0, op.op, ": 0 < keep <= 1");
+}
+
+// fp32 split-K planes of the contract kernels (none when one slice does)
+float* contract_part(Tensor& part, const Tensor& t, int K, long M, int r) {
   const int nsplit = lora_contract_ksplit(K, M, r);
-  torch::Tensor part;
-  float* part_ptr = nullptr;
-  if (nsplit > 1) {
-    part = torch::empty({nsplit, M, r}, x.options().dtype(torch::kFloat));
-    part_ptr = part.data_ptr<float>();
-  }
-  launch_lora_contract(x.data_ptr(), w.data_ptr(),
-                       opt_mask(mask, x.numel(), "mask"), part_ptr,
+  if (nsplit <= 1) return nullptr;
+  part = torch::empty({nsplit, t.numel()}, t.options());
+  return part.data_ptr<float>();
+}
+
+Tensor lora_contract(Tensor x, Tensor w, OptTensor mask, int64_t seed,
+                     double keep) {
+  const Op op("lora_contract", x, BF16, "x");
+  const long M = lora_rows(op, x, "x");
+  const int K = i32(x.size(-1)), r = lora_rank(op, w, "w", K, 64);
+  check_keep(op, keep);
+  const void* mk = op.opt(mask, BF16, "mask", x.numel());
+  op.aligned16("mask", {mk});
+  auto t = torch::empty({M, r}, x.options().dtype(F32));
+  if (M == 0) return t;
+  Tensor part;
+  float* part_ptr = contract_part(part, t, K, M, r);
+  launch_lora_contract(x.data_ptr(), w.data_ptr(), mk, part_ptr,
                        t.data_ptr<float>(), M, K, r,
-                       (unsigned long long)seed, (float)keep,
-                       cur_stream());
+                       (unsigned long long)seed, (float)keep, op.stream);
   return t;
 }
 
 // Two adapters, two dropout seeds, one pass over x: (t0, t1), each
 // bit-identical to lora_contract with its own adapter and seed.
-std::vector<torch::Tensor> lora_contract2(torch::Tensor x, torch::Tensor w0,
-                                          torch::Tensor w1, int64_t seed0,
-                                          int64_t seed1, double keep) {
-  check_bf16_contig(x, "x");
-  check_bf16_contig(w0, "w0");
-  check_bf16_contig(w1, "w1");
-  const int K = (int)x.size(-1);
-  const long M = x.numel() / K;
-  const int r = (int)w0.size(0);
-  TORCH_CHECK(w0.dim() == 2 && w0.sizes() == w1.sizes() && w0.size(1) == K,
-              "w0/w1 [r,K] mismatch");
-  TORCH_CHECK(r >= 1 && r <= 16, "lora_contract2: r <= 16");
-  TORCH_CHECK(K % 8 == 0);
-  auto t = torch::empty({2, M, r}, x.options().dtype(torch::kFloat));
-  const int nsplit = lora_contract_ksplit(K, M, r);
-  torch::Tensor part;
-  float* part_ptr = nullptr;
-  if (nsplit > 1) {
-    part = torch::empty({nsplit, 2, M, r},
-                        x.options().dtype(torch::kFloat));
-    part_ptr = part.data_ptr<float>();
-  }
+std::vector<Tensor> lora_contract2(Tensor x, Tensor w0, Tensor w1,
+                                   int64_t seed0, int64_t seed1,
+                                   double keep) {
+  const Op op("lora_contract2", x, BF16, "x");
+  const long M = lora_rows(op, x, "x");
+  const int K = i32(x.size(-1)), r = lora_rank(op, w0, "w0", K, 16);
+  op.shape(w1, w0.sizes(), "w1");
+  lora_rank(op, w1, "w1", K, 16);
+  check_keep(op, keep);
+  auto t = torch::empty({2, M, r}, x.options().dtype(F32));
+  if (M == 0) return {t[0], t[1]};
+  Tensor part;
+  float* part_ptr = contract_part(part, t, K, M, r);
   launch_lora_contract2(x.data_ptr(), w0.data_ptr(), w1.data_ptr(),
                         part_ptr, t.data_ptr<float>(), M, K, r,
                         (unsigned long long)seed0,
                         (unsigned long long)seed1, (float)keep,
-                        cur_stream());
+                        op.stream);
   return {t[0], t[1]};
 }
 
 // wt is the adapter already in [r,N] (lora_B transposed, or lora_A as it
 // is for the dx term): no transposed copy per call.
-void lora_expand_add_t(torch::Tensor y, torch::Tensor t, torch::Tensor wt,
-                       double scale, c10::optional<torch::Tensor> mask,
-                       int64_t seed, double keep) {
-  check_bf16_contig(y, "y");
-  check_bf16_contig(wt, "wt");
-  const int N = (int)y.size(-1);
-  const long M = y.numel() / N;
-  const int r = (int)wt.size(0);
-  TORCH_CHECK(wt.dim() == 2 && wt.size(1) == N, "wt [r,N] mismatch");
-  TORCH_CHECK(t.scalar_type() == torch::kFloat && t.is_contiguous() &&
-              t.numel() == M * r, "t [M,r] f32");
+void lora_expand_add_t(Tensor y, Tensor t, Tensor wt, double scale,
+                       OptTensor mask, int64_t seed, double keep) {
+  const Op op("lora_expand_add_t", y, BF16, "y");
+  const long M = lora_rows(op, y, "y");
+  const int N = i32(y.size(-1)), r = lora_rank(op, wt, "wt", N);
+  check_keep(op, keep);
+  op.dense(t, F32, "t", M * r);
+  const void* mk = op.opt(mask, BF16, "mask", y.numel());
+  op.aligned16("mask", {mk});
   TORCH_CHECK(keep >= 1.0 || lora_expand_rng_ok(M, N, r),
               "RNG dropout needs the r<=16 fast path; materialize the "
               "mask for this shape");
+  if (M == 0) return;
   launch_lora_expand_add(y.data_ptr(), t.data_ptr<float>(), wt.data_ptr(),
-                         opt_mask(mask, y.numel(), "mask"), M, N, r,
-                         (float)scale, (unsigned long long)seed,
-                         (float)keep, cur_stream());
+                         mk, M, N, r, (float)scale,
+                         (unsigned long long)seed, (float)keep,
+                         op.stream);
 }
 
 // y += mask0 o (s * t0 @ a0) + mask1 o (s * t1 @ a1), a0/a1 [r,N]: one
 // read-modify-write of y, one rounding.
-void lora_expand_add2(torch::Tensor y, torch::Tensor t0, torch::Tensor t1,
-                      torch::Tensor a0, torch::Tensor a1, double scale,
-                      int64_t seed0, int64_t seed1, double keep) {
-  check_bf16_contig(y, "y");
-  check_bf16_contig(a0, "a0");
-  check_bf16_contig(a1, "a1");
-  const int N = (int)y.size(-1);
-  const long M = y.numel() / N;
-  const int r = (int)a0.size(0);
-  TORCH_CHECK(a0.dim() == 2 && a0.sizes() == a1.sizes() && a0.size(1) == N,
-              "a0/a1 [r,N] mismatch");
-  TORCH_CHECK(r >= 1 && r <= 16 && N % 8 == 0,
-              "lora_expand_add2: r <= 16, N % 8 == 0");
-  for (const auto& t : {t0, t1})
-    TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kFloat &&
-                t.is_contiguous() && t.numel() == M * r, "t [M,r] f32");
+void lora_expand_add2(Tensor y, Tensor t0, Tensor t1, Tensor a0, Tensor a1,
+                      double scale, int64_t seed0, int64_t seed1,
+                      double keep) {
+  const Op op("lora_expand_add2", y, BF16, "y");
+  const long M = lora_rows(op, y, "y");
+  const int N = i32(y.size(-1)), r = lora_rank(op, a0, "a0", N, 16);
+  op.shape(a1, a0.sizes(), "a1");
+  lora_rank(op, a1, "a1", N, 16);
+  check_keep(op, keep);
+  op.dense(t0, F32, "t0", M * r);
+  op.dense(t1, F32, "t1", M * r);
   if (M == 0) return;
   launch_lora_expand_add_dual(y.data_ptr(), t0.data_ptr<float>(),
                               t1.data_ptr<float>(), a0.data_ptr(),
                               a1.data_ptr(), M, N, r, (float)scale,
                               (unsigned long long)seed0,
                               (unsigned long long)seed1, (float)keep,
-                              cur_stream());
+                              op.stream);
 }
 
-torch::Tensor lora_wgrad(torch::Tensor t, torch::Tensor x, double scale,
-                         c10::optional<torch::Tensor> mask,
-                         int64_t seed, double keep) {
-  check_bf16_contig(x, "x");
-  TORCH_CHECK(t.scalar_type() == torch::kFloat && t.is_contiguous());
-  const int K = (int)x.size(-1);
-  const long M = x.numel() / K;
-  const int r = (int)t.size(-1);
-  auto out = torch::empty({r, K}, x.options().dtype(torch::kFloat));
-  const int sm = lora_wgrad_splitm(K, r, M);
-  auto part = torch::empty({sm, r, K}, x.options().dtype(torch::kFloat));
-  launch_lora_wgrad(t.data_ptr<float>(), x.data_ptr(),
-                    opt_mask(mask, x.numel(), "mask"),
+Tensor lora_wgrad(Tensor t, Tensor x, double scale, OptTensor mask,
+                  int64_t seed, double keep) {
+  const Op op("lora_wgrad", x, BF16, "x");
+  const long M = lora_rows(op, x, "x");
+  const int K = i32(x.size(-1));
+  const int r = op.dense(t, F32, "t").dim() >= 1 ? i32(t.size(-1)) : 0;
+  TORCH_CHECK(r >= 1 && t.numel() == M * r, "lora_wgrad: t must be [M,r] ",
+              "with M = ", M, ", r >= 1, got ", t.sizes());
+  check_keep(op, keep);
+  const void* mk = op.opt(mask, BF16, "mask", x.numel());
+  op.aligned16("mask", {mk});
+  if (M == 0) return torch::zeros({r, K}, x.options().dtype(F32));
+  auto out = torch::empty({r, K}, x.options().dtype(F32));
+  auto part = torch::empty({lora_wgrad_splitm(K, r, M), r, K},
+                           out.options());
+  launch_lora_wgrad(t.data_ptr<float>(), x.data_ptr(), mk,
                     part.data_ptr<float>(), out.data_ptr<float>(), M, K, r,
                     (float)scale, (unsigned long long)seed, (float)keep,
-                    cur_stream());
+                    op.stream);
   return out;
 }
 
-// Materialize the RNG dropout mask (bit-identical to what the fused
-// MODE==2 kernels consume) — used by tests and the r>16 fallback.
-torch::Tensor dropout_mask(int64_t M, int64_t K, int64_t seed, double keep,
-                           torch::Tensor like) {
-  TORCH_CHECK((M * K) % 8 == 0, "M*K % 8 == 0");
-  auto m = torch::empty({M, K}, like.options().dtype(torch::kBFloat16));
+// Materialize the RNG dropout mask (bit-identical to what the fused MODE==2
+// kernels consume): tests and the r>16 fallback. `like` names the device.
+Tensor dropout_mask(int64_t M, int64_t K, int64_t seed, double keep,
+                    Tensor like) {
+  const Op op("dropout_mask", like, "like");
+  TORCH_CHECK(M >= 0 && K >= 0 && (M * K) % 8 == 0,
+              "dropout_mask: M*K % 8 == 0");
+  check_keep(op, keep);
+  auto m = torch::empty({M, K}, like.options().dtype(BF16));
+  if (M * K == 0) return m;
   launch_dropout_mask(m.data_ptr(), M * K, (unsigned long long)seed,
-                      (float)keep, cur_stream());
+                      (float)keep, op.stream);
   return m;
 }
 
 // ---------------------------------------------------------------- AdamW
-void adamw(torch::Tensor p, torch::Tensor master, torch::Tensor grad,
-           torch::Tensor m, torch::Tensor v, double lr, double b1, double b2,
-           double eps, double wd, long step) {
-  check_bf16_contig(p, "p");
-  TORCH_CHECK(master.scalar_type() == torch::kFloat);
-  TORCH_CHECK(grad.scalar_type() == torch::kFloat);
-  TORCH_CHECK(p.numel() % 4 == 0, "flat param buffer must be padded to 4");
+void adamw(Tensor p, Tensor master, Tensor grad, Tensor m, Tensor v,
+           double lr, double b1, double b2, double eps, double wd,
+           long step) {
+  const Op op("adamw", p, BF16, "p");
+  const long n = p.numel();
+  TORCH_CHECK(n % 4 == 0, "flat param buffer must be padded to 4");
+  TORCH_CHECK(step >= 1 && step <= INT_MAX, "adamw: step must be >= 1");
+  op.dense(master, F32, "master", n);
+  op.dense(grad, F32, "grad", n);
+  op.dense(m, F32, "m", n);
+  op.dense(v, F32, "v", n);
+  op.aligned16("master, grad, m, v", {master.data_ptr(), grad.data_ptr(),
+                                      m.data_ptr(), v.data_ptr()});
+  if (n == 0) return;
   launch_adamw(p.data_ptr(), master.data_ptr<float>(),
                grad.data_ptr<float>(), m.data_ptr<float>(),
-               v.data_ptr<float>(), p.numel(), (float)lr, (float)b1,
-               (float)b2, (float)eps, (float)wd, (int)step, cur_stream());
+               v.data_ptr<float>(), n, (float)lr, (float)b1, (float)b2,
+               (float)eps, (float)wd, (int)step, op.stream);
 }
 
-torch::Tensor l2_norm(torch::Tensor x) {
-  TORCH_CHECK(x.is_cuda() && x.scalar_type() == torch::kFloat &&
-              x.is_contiguous());
+Tensor l2_norm(Tensor x) {
+  const Op op("l2_norm", x, F32, "x");
   auto ws = torch::empty({1024}, x.options());
   auto out = torch::empty({1}, x.options());
   launch_l2_norm(x.data_ptr<float>(), ws.data_ptr<float>(),
-                 out.data_ptr<float>(), x.numel(), cur_stream());
+                 out.data_ptr<float>(), x.numel(), op.stream);
   return out;
 }
 
 // ------------------------------------------------------------ attention
 // [B,S,H,D] -> [B,H,D,S]
-torch::Tensor transpose_sd(torch::Tensor x) {
-  check_bf16_contig(x, "x");
-  TORCH_CHECK(x.dim() == 4, "x must be [B,S,H,D]");
-  const int B = (int)x.size(0), S = (int)x.size(1), H = (int)x.size(2),
-            D = (int)x.size(3);
+Tensor transpose_sd(Tensor x) {
+  const Op op("transpose_sd", x, BF16, "x");
+  TORCH_CHECK(x.dim() == 4, "transpose_sd: x must be [B,S,H,D]");
+  const int B = i32(x.size(0)), S = i32(x.size(1)), H = i32(x.size(2)),
+            D = i32(x.size(3));
+  TORCH_CHECK(D % 64 == 0, "transpose_sd: D % 64");
+  op.aligned16("x", {x.data_ptr()});
   auto xt = torch::empty({B, H, D, S}, x.options());
+  if (x.numel() == 0) return xt;
   launch_transpose_sd(x.data_ptr(), xt.data_ptr(), B, S, H, D,
-                      cur_stream());
+                      op.stream);
   return xt;
 }
 
-// q: [B,S,Hq,D]; k, v: [B,Skv,Hkv,D] — all BSHD, v row-major like k.
-std::vector<torch::Tensor> attn_fwd(torch::Tensor q, torch::Tensor k,
-                                    torch::Tensor v, bool causal,
-                                    double scale,
-                                    c10::optional<torch::Tensor> doc_start) {
-  check_bf16_contig(q, "q");
-  check_bf16_contig(k, "k");
-  check_bf16_contig(v, "v");
-  const int B = (int)q.size(0), S = (int)q.size(1), Hq = (int)q.size(2),
-            D = (int)q.size(3);
-  const int Skv = (int)k.size(1), Hkv = (int)k.size(2);
-  TORCH_CHECK(v.size(1) == Skv && v.size(2) == Hkv && v.size(3) == D,
-              "v must be BSHD like k");
-  TORCH_CHECK(D == 64 || D == 128, "D must be 64 or 128");
-  TORCH_CHECK(Hq % Hkv == 0, "GQA group");
-  const int* dsp = doc_map_ptr(doc_start, B, S, "doc_start");
-  if (dsp) check_docs_shape(causal, S, Skv);
+// q [B,S,Hq,D] (the Op's first tensor); k, v [B,Skv,Hkv,D] — all BSHD, v
+// row-major like k. The launchers run nothing for another D.
+struct AttnShape { int B, S, Hq, D, Skv, Hkv; };
+
+AttnShape check_attn(const Op& op, const Tensor& q, const Tensor& k,
+                     const Tensor& v) {
+  TORCH_CHECK(q.dim() == 4, op.op, ": q must be [B,S,Hq,D]");
+  const long B = q.size(0), D = q.size(3);
+  TORCH_CHECK(D == 64 || D == 128, op.op, ": D must be 64 or 128");
+  op.dense(k, BF16, "k");
+  TORCH_CHECK(k.dim() == 4 && k.size(0) == B && k.size(3) == D, op.op,
+              ": k must be [B,Skv,Hkv,D], got ", k.sizes());
+  op.shape(op.dense(v, BF16, "v"), k.sizes(), "v");
+  const AttnShape a{i32(B), i32(q.size(1)), i32(q.size(2)),
+                    i32(D), i32(k.size(1)), i32(k.size(2))};
+  TORCH_CHECK(a.S >= 1 && a.Skv >= 1, op.op, ": S >= 1 and Skv >= 1");
+  TORCH_CHECK(a.Hkv >= 1 && a.Hq >= 1 && a.Hq % a.Hkv == 0, op.op,
+              ": Hq % Hkv (GQA group)");
+  op.aligned16("q, k, v", {q.data_ptr(), k.data_ptr(), v.data_ptr()});
+  return a;
+}
+
+std::vector<Tensor> attn_fwd(Tensor q, Tensor k, Tensor v, bool causal,
+                             double scale, OptTensor doc_start) {
+  const Op op("attn_fwd", q, BF16, "q");
+  const AttnShape a = check_attn(op, q, k, v);
+  const int* dsp = doc_map(op, doc_start, a.B, a.S, "doc_start");
+  if (dsp) check_docs_shape(causal, a.S, a.Skv);
   auto o = torch::empty_like(q);
-  auto lse = torch::empty({B, Hq, S}, q.options().dtype(torch::kFloat));
+  auto lse = torch::empty({a.B, a.Hq, a.S}, q.options().dtype(F32));
+  if (a.B == 0) return {o, lse};
   launch_attn_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
-                  lse.data_ptr<float>(), dsp, B, Hq, Hkv, S, Skv, D,
-                  (float)scale, causal ? 1 : 0, cur_stream());
+                  lse.data_ptr<float>(), dsp, a.B, a.Hq, a.Hkv, a.S, a.Skv,
+                  a.D, (float)scale, causal ? 1 : 0, op.stream);
   return {o, lse};
 }
 
 // C[M,N] = A[M,K] @ B[N,K]^T (+ optional bf16 src) — the hand-written
 // 256x256-tile MFMA GEMM (gemm.hip). Requires N % 256 == 0, K % 64 == 0,
 // K >= 128; any M (SRSRC-clamped tail).
-torch::Tensor gemm_nt(torch::Tensor a, torch::Tensor b,
-                      c10::optional<torch::Tensor> src) {
-  check_bf16_contig(a, "a");
-  check_bf16_contig(b, "b");
-  const int K = (int)b.size(1), N = (int)b.size(0);
-  const long M = a.numel() / K;
-  TORCH_CHECK(a.size(-1) == K, "gemm_nt: inner dims");
+Tensor gemm_nt(Tensor a, Tensor b, OptTensor src) {
+  const Op op("gemm_nt", a, BF16, "a");
+  TORCH_CHECK(op.dense(b, BF16, "b").dim() == 2, "gemm_nt: b must be [N,K]");
+  const int K = i32(b.size(1)), N = i32(b.size(0));
   TORCH_CHECK(N % 256 == 0 && K % 64 == 0 && K >= 128,
               "gemm_nt: unsupported shape N=", N, " K=", K);
+  const long M = op.rows(a, "a", K);
+  const void* sp = op.opt(src, BF16, "src", M * (long)N);
+  op.aligned16("a, b, src", {a.data_ptr(), b.data_ptr(), sp});
   auto sizes = a.sizes().vec();
-  sizes[sizes.size() - 1] = N;
+  sizes.back() = N;
   auto c = torch::empty(sizes, a.options());
-  const void* sp = nullptr;
-  if (src.has_value()) {
-    check_bf16_contig(*src, "src");
-    TORCH_CHECK(src->numel() == M * N, "gemm_nt: src shape");
-    sp = src->data_ptr();
-  }
+  if (M == 0 || N == 0) return c;
   launch_gemm_nt(a.data_ptr(), b.data_ptr(), sp, c.data_ptr(), M, N, K,
-                 cur_stream());
+                 op.stream);
   return c;
 }
 
-// weight-only dequant (int8 per-row / int4 group-64) -> bf16
-torch::Tensor dequant_int8(torch::Tensor q, torch::Tensor scale) {
-  TORCH_CHECK(q.is_cuda() && q.scalar_type() == torch::kChar &&
-              q.is_contiguous());
-  const int K = (int)q.size(1);
+// weight-only dequant (int8 per-row / int4 group-wise) -> bf16
+Tensor dequant_int8(Tensor q, Tensor scale) {
+  const Op op("dequant_int8", q, torch::kChar, "q");
+  TORCH_CHECK(q.dim() == 2, "dequant_int8: q must be [N,K]");
   const long N = q.size(0);
-  TORCH_CHECK(K % 8 == 0, "K % 8");
-  auto out = torch::empty({N, K},
-                          q.options().dtype(torch::kBFloat16));
+  const int K = i32(q.size(1));
+  TORCH_CHECK(K % 8 == 0, "dequant_int8: K % 8");
+  op.dense(scale, F32, "scale", N);
+  auto out = torch::empty({N, K}, q.options().dtype(BF16));
+  if (q.numel() == 0) return out;
   launch_dequant_int8(q.data_ptr(), scale.data_ptr<float>(),
-                      out.data_ptr(), N, K, cur_stream());
+                      out.data_ptr(), N, K, op.stream);
   return out;
 }
 
-torch::Tensor dequant_int4(torch::Tensor packed, torch::Tensor scale,
-                           long group) {
-  TORCH_CHECK(packed.is_cuda() && packed.scalar_type() == torch::kByte &&
-              packed.is_contiguous());
-  const int K = (int)packed.size(1) * 2;
+Tensor dequant_int4(Tensor packed, Tensor scale, long group) {
+  const Op op("dequant_int4", packed, torch::kByte, "packed");
+  TORCH_CHECK(packed.dim() == 2, "dequant_int4: packed must be [N,K/2]");
   const long N = packed.size(0);
-  TORCH_CHECK(K % 8 == 0 && group % 8 == 0, "K/group alignment");
-  auto out = torch::empty({N, K},
-                          packed.options().dtype(torch::kBFloat16));
+  const int K = i32(packed.size(1) * 2);
+  TORCH_CHECK(K % 8 == 0 && group > 0 && group % 8 == 0 && K % group == 0,
+              "dequant_int4: K % 8, group % 8, K % group");
+  op.dense(scale, F32, "scale", N * (K / group));
+  auto out = torch::empty({N, K}, packed.options().dtype(BF16));
+  if (packed.numel() == 0) return out;
   launch_dequant_int4(packed.data_ptr(), scale.data_ptr<float>(),
-                      out.data_ptr(), N, K, (int)group, cur_stream());
+                      out.data_ptr(), N, K, i32(group), op.stream);
   return out;
 }
 
-// chunked-vocab CE: online LSE merge over one logits chunk (in-place
-// m/l/tgt update) and the per-chunk dlogits for the dX sweep.
-void xent_lse_merge(torch::Tensor logits, torch::Tensor targets,
-                    torch::Tensor m_run, torch::Tensor l_run,
-                    torch::Tensor tgt, long v0, long ignore_index) {
-  check_bf16_contig(logits, "logits");
-  const int Vc = (int)logits.size(-1);
-  const long N = logits.numel() / Vc;
-  TORCH_CHECK(Vc % 8 == 0, "Vc % 8");
-  launch_xent_lse_merge(logits.data_ptr(), targets.data_ptr<long>(),
-                        m_run.data_ptr<float>(), l_run.data_ptr<float>(),
-                        tgt.data_ptr<float>(), N, Vc, v0, ignore_index,
-                        cur_stream());
-}
-
-torch::Tensor xent_dlogits(torch::Tensor logits, torch::Tensor targets,
-                           torch::Tensor lse, long v0, long ignore_index) {
-  check_bf16_contig(logits, "logits");
-  const int Vc = (int)logits.size(-1);
-  const long N = logits.numel() / Vc;
-  TORCH_CHECK(Vc % 8 == 0, "Vc % 8");
-  auto dl = torch::empty_like(logits);
-  launch_xent_dlogits(logits.data_ptr(), targets.data_ptr<long>(),
-                      lse.data_ptr<float>(), dl.data_ptr(), N, Vc, v0,
-                      ignore_index, cur_stream());
-  return dl;
-}
-
-// y[1,N] = x[1,K] @ W[N,K]^T (decode GEMV; fp32 accumulate)
-torch::Tensor gemv(torch::Tensor x, torch::Tensor w) {
-  check_bf16_contig(x, "x");
-  check_bf16_contig(w, "w");
-  const int K = (int)w.size(1), N = (int)w.size(0);
-  TORCH_CHECK(x.numel() == K, "gemv wants a single row");
-  TORCH_CHECK(K % 8 == 0, "K % 8");
+// y[..., N] = x[..., K] @ W[N,K]^T, one row x (decode GEMV; fp32 accumulate)
+Tensor gemv(Tensor x, Tensor w) {
+  const Op op("gemv", x, BF16, "x");
+  TORCH_CHECK(op.dense(w, BF16, "w").dim() == 2, "gemv: w must be [N,K]");
+  const int K = i32(w.size(1)), N = i32(w.size(0));
+  TORCH_CHECK(K % 8 == 0, "gemv: K % 8");
+  TORCH_CHECK(op.rows(x, "x", K) == 1, "gemv wants a single row");
+  op.aligned16("x, w", {x.data_ptr(), w.data_ptr()});
   auto sizes = x.sizes().vec();
-  sizes[sizes.size() - 1] = N;
+  sizes.back() = N;
   auto y = torch::empty(sizes, x.options());
+  if (N == 0) return y;
   launch_gemv_bf16(x.data_ptr(), w.data_ptr(), y.data_ptr(), N, K,
-                   cur_stream());
+                   op.stream);
   return y;
 }
 
 // Quantized decode: y[M,N] = x[M,K] @ dequant(Wq)[N,K]^T for M <= 16
 // rows (the flattened leading dims of x), streaming the integer weight
 // (qgemv.hip). Only allocation is the output: hipGraph-capturable.
-static torch::Tensor qgemv_out(const torch::Tensor& x, int N) {
+// Checks x [M,K] against the weight [N, cols] and its `nscale` scales,
+// allocates y.
+Tensor qgemv_out(const Op& op, const Tensor& x, const Tensor& w,
+                 at::ScalarType wt, const Tensor& scale, int K,
+                 long nscale) {
+  op.dense(w, wt, "weight");
+  op.dense(scale, F32, "scale", nscale);
+  const long M = op.rows(x, "x", K);
+  TORCH_CHECK(M >= 1 && M <= 16, "qgemv: 1 <= M <= 16, got ", M);
+  op.aligned16("x, weight", {x.data_ptr(), w.data_ptr()});
   auto sizes = x.sizes().vec();
-  sizes[sizes.size() - 1] = N;
+  sizes.back() = w.size(0);
   return torch::empty(sizes, x.options());
 }
 
-static long qgemv_rows(const torch::Tensor& x, int K) {
-  check_bf16_contig(x, "x");
-  TORCH_CHECK(x.dim() >= 1 && x.size(-1) == K, "qgemv: x inner dim != K");
-  const long M = x.numel() / K;
-  TORCH_CHECK(M >= 1 && M <= 16, "qgemv: 1 <= M <= 16, got ", M);
-  TORCH_CHECK((uintptr_t)x.data_ptr() % 16 == 0, "qgemv: x 16-B aligned");
-  return M;
-}
-
-static void qgemv_check_w(const torch::Tensor& w, at::ScalarType dt,
-                          const torch::Tensor& scale, long nscale) {
-  TORCH_CHECK(w.is_cuda() && w.scalar_type() == dt && w.dim() == 2 &&
-              w.is_contiguous(), "qgemv: weight dtype/layout");
-  TORCH_CHECK((uintptr_t)w.data_ptr() % 16 == 0,
-              "qgemv: weight 16-B aligned");
-  TORCH_CHECK(scale.is_cuda() && scale.scalar_type() == torch::kFloat &&
-              scale.is_contiguous() && scale.numel() == nscale,
-              "qgemv: scale dtype/shape");
-}
-
-torch::Tensor qgemv_int8(torch::Tensor x, torch::Tensor q,
-                         torch::Tensor scale) {
-  const int N = (int)q.size(0), K = (int)q.size(1);
+Tensor qgemv_int8(Tensor x, Tensor q, Tensor scale) {
+  const Op op("qgemv_int8", x, BF16, "x");
+  TORCH_CHECK(q.dim() == 2, "qgemv_int8: q must be [N,K]");
+  const int N = i32(q.size(0)), K = i32(q.size(1));
   TORCH_CHECK(K > 0 && K % 16 == 0, "qgemv_int8: K % 16");
-  qgemv_check_w(q, torch::kChar, scale, N);
-  const long M = qgemv_rows(x, K);
-  auto y = qgemv_out(x, N);
+  auto y = qgemv_out(op, x, q, torch::kChar, scale, K, N);
+  if (N == 0) return y;
   launch_qgemv_int8(x.data_ptr(), q.data_ptr(), scale.data_ptr<float>(),
-                    y.data_ptr(), (int)M, N, K, cur_stream());
+                    y.data_ptr(), i32(x.numel() / K), N, K, op.stream);
   return y;
 }
 
-torch::Tensor qgemv_int4(torch::Tensor x, torch::Tensor packed,
-                         torch::Tensor scale, long group) {
-  const int N = (int)packed.size(0), K = (int)packed.size(1) * 2;
+Tensor qgemv_int4(Tensor x, Tensor packed, Tensor scale, long group) {
+  const Op op("qgemv_int4", x, BF16, "x");
+  TORCH_CHECK(packed.dim() == 2, "qgemv_int4: packed must be [N,K/2]");
+  const int N = i32(packed.size(0)), K = i32(packed.size(1) * 2);
   TORCH_CHECK(K > 0 && K % 32 == 0, "qgemv_int4: K % 32");
   TORCH_CHECK(group > 0 && group % 32 == 0 && K % group == 0,
               "qgemv_int4: group % 32, K % group");
-  qgemv_check_w(packed, torch::kByte, scale, (long)N * (K / group));
-  const long M = qgemv_rows(x, K);
-  auto y = qgemv_out(x, N);
+  auto y = qgemv_out(op, x, packed, torch::kByte, scale, K,
+                     (long)N * (K / group));
+  if (N == 0) return y;
   launch_qgemv_int4(x.data_ptr(), packed.data_ptr(),
-                    scale.data_ptr<float>(), y.data_ptr(), (int)M, N, K,
-                    (int)group, cur_stream());
+                    scale.data_ptr<float>(), y.data_ptr(), i32(x.numel() / K),
+                    N, K, i32(group), op.stream);
   return y;
 }
 
@@ -634,179 +660,152 @@ torch::Tensor qgemv_int4(torch::Tensor x, torch::Tensor packed,
 // [0,G) are left untouched. Nothing here looks at idx's content and the
 // only allocation is t, so the call is hipGraph-capturable and a replay
 // follows whatever idx holds by then.
-void mlora_add(torch::Tensor y, torch::Tensor x, torch::Tensor A,
-               torch::Tensor Bt, torch::Tensor scale, torch::Tensor idx) {
-  check_bf16_contig(y, "y");
-  check_bf16_contig(x, "x");
-  check_bf16_contig(A, "A");
-  check_bf16_contig(Bt, "Bt");
+void mlora_add(Tensor y, Tensor x, Tensor A, Tensor Bt, Tensor scale,
+               Tensor idx) {
+  const Op op("mlora", y, BF16, "y");
+  op.dense(x, BF16, "x");
+  op.dense(A, BF16, "A");
+  op.dense(Bt, BF16, "Bt");
   TORCH_CHECK(y.dim() == 2 && x.dim() == 2 && A.dim() == 3 && Bt.dim() == 3,
               "mlora: y [M,N], x [M,K], A [G,R,K], Bt [G,R,N]");
-  const long M = x.size(0), K = x.size(1), N = y.size(1);
-  const long G = A.size(0), R = A.size(1);
+  const int M = i32(x.size(0)), K = i32(x.size(1)), N = i32(y.size(1));
+  const int G = i32(A.size(0)), R = i32(A.size(1));
   TORCH_CHECK(y.size(0) == M, "mlora: y/x rows differ");
-  TORCH_CHECK(A.size(2) == K && Bt.size(0) == G && Bt.size(1) == R &&
-              Bt.size(2) == N, "mlora: A [G,R,K] / Bt [G,R,N] mismatch");
+  TORCH_CHECK(A.size(2) == K, "mlora: A [G,R,K] / Bt [G,R,N] mismatch");
+  op.shape(Bt, {G, R, N}, "Bt");
   TORCH_CHECK(M >= 1 && M <= 16, "mlora: 1 <= M <= 16, got ", M);
   TORCH_CHECK(K >= 8 && K % 8 == 0 && N >= 8 && N % 8 == 0,
               "mlora: K % 8, N % 8");
   TORCH_CHECK(R == 8 || R == 16 || R == 32 || R == 64,
               "mlora: R must be 8, 16, 32 or 64, got ", R);
-  TORCH_CHECK(G >= 1 && G * R * std::max(K, N) < (1L << 40),
+  TORCH_CHECK(G >= 1 && (long)G * R * std::max(K, N) < (1L << 40),
               "mlora: stack size");
-  TORCH_CHECK(scale.is_cuda() && scale.scalar_type() == torch::kFloat &&
-              scale.is_contiguous() && scale.numel() == G,
-              "mlora: scale must be f32 [G] on the GPU");
-  TORCH_CHECK(idx.is_cuda() && idx.scalar_type() == torch::kInt &&
-              idx.is_contiguous() && idx.numel() == M,
-              "mlora: idx must be int32 [M] on the GPU");
-  TORCH_CHECK((uintptr_t)y.data_ptr() % 16 == 0 &&
-              (uintptr_t)x.data_ptr() % 16 == 0 &&
-              (uintptr_t)A.data_ptr() % 16 == 0 &&
-              (uintptr_t)Bt.data_ptr() % 16 == 0, "mlora: 16-B alignment");
-  auto t = torch::empty({M, R}, x.options().dtype(torch::kFloat));
+  op.dense(scale, F32, "scale", G);
+  op.dense(idx, I32, "idx", M);
+  op.aligned16("y, x, A, Bt", {y.data_ptr(), x.data_ptr(), A.data_ptr(),
+                               Bt.data_ptr()});
+  auto t = torch::empty({M, R}, x.options().dtype(F32));
   launch_mlora_shrink(x.data_ptr(), A.data_ptr(), idx.data_ptr<int>(),
-                      t.data_ptr<float>(), (int)M, (int)K, (int)R, (int)G,
-                      cur_stream());
+                      t.data_ptr<float>(), M, K, R, G, op.stream);
   launch_mlora_expand_add(y.data_ptr(), t.data_ptr<float>(), Bt.data_ptr(),
-                          scale.data_ptr<float>(), idx.data_ptr<int>(),
-                          (int)M, (int)N, (int)R, (int)G, cur_stream());
+                          scale.data_ptr<float>(), idx.data_ptr<int>(), M,
+                          N, R, G, op.stream);
 }
 
 // Per-row sampling of a decode batch (sample.hip): every parameter is a
 // device tensor the kernel reads at run time and the only allocation is
 // the output, so the call is hipGraph-capturable and a replay follows
 // whatever the parameter buffers hold by then.
-torch::Tensor sample(torch::Tensor logits, torch::Tensor temperature,
-                     torch::Tensor top_p, torch::Tensor top_k,
-                     torch::Tensor seed, torch::Tensor offset,
-                     c10::optional<torch::Tensor> u) {
-  TORCH_CHECK(logits.is_cuda() && logits.scalar_type() == torch::kBFloat16,
-              "sample: logits must be bf16 on the GPU");
+Tensor sample(Tensor logits, Tensor temperature, Tensor top_p, Tensor top_k,
+              Tensor seed, Tensor offset, OptTensor u) {
+  const Op op("sample", logits, BF16, "logits", /*contiguous=*/false);
   TORCH_CHECK(logits.dim() == 2, "sample: logits must be [B, V]");
-  const long B = logits.size(0), V = logits.size(1);
+  const int B = i32(logits.size(0)), V = i32(logits.size(1));
   TORCH_CHECK(V > 0 && V % 8 == 0, "sample: V % 8, got V = ", V);
   TORCH_CHECK(V <= sample_max_vocab(), "sample: V = ", V,
               " is above the kernel limit of ", sample_max_vocab());
   TORCH_CHECK(logits.stride(1) == 1, "sample: logits rows must be dense");
   TORCH_CHECK(B <= 1 || (logits.stride(0) >= 0 && logits.stride(0) % 8 == 0),
               "sample: row stride % 8");
-  TORCH_CHECK((uintptr_t)logits.data_ptr() % 16 == 0,
-              "sample: logits need 16-B alignment");
-  auto par = [&](const torch::Tensor& t, torch::ScalarType ty,
-                 const char* name) {
-    TORCH_CHECK(t.is_cuda() && t.get_device() == logits.get_device() &&
-                t.scalar_type() == ty && t.dim() == 1 && t.size(0) == B &&
-                t.is_contiguous(),
-                "sample: ", name, " must be a contiguous ", ty, " [", B,
-                "] tensor on the logits' device");
-  };
-  par(temperature, torch::kFloat, "temperature");
-  par(top_p, torch::kFloat, "top_p");
-  par(top_k, torch::kInt, "top_k");
-  par(seed, torch::kLong, "seed");
-  par(offset, torch::kInt, "offset");
-  const float* up = nullptr;
-  if (u.has_value()) {
-    par(*u, torch::kFloat, "u");
-    up = u->data_ptr<float>();
-  }
-  auto out = torch::empty({B}, logits.options().dtype(torch::kLong));
+  op.aligned16("logits", {logits.data_ptr()});
+  op.shape(op.dense(temperature, F32, "temperature"), {B}, "temperature");
+  op.shape(op.dense(top_p, F32, "top_p"), {B}, "top_p");
+  op.shape(op.dense(top_k, I32, "top_k"), {B}, "top_k");
+  op.shape(op.dense(seed, I64, "seed"), {B}, "seed");
+  op.shape(op.dense(offset, I32, "offset"), {B}, "offset");
+  if (u.has_value()) op.shape(*u, {B}, "u");
+  const float* up = op.opt<float>(u, F32, "u");
+  auto out = torch::empty({B}, logits.options().dtype(I64));
   if (B == 0) return out;
-  launch_sample(logits.data_ptr(), B > 1 ? logits.stride(0) : V, (int)B,
-                (int)V, temperature.data_ptr<float>(),
-                top_p.data_ptr<float>(), top_k.data_ptr<int>(),
+  launch_sample(logits.data_ptr(), B > 1 ? logits.stride(0) : (long)V, B, V,
+                temperature.data_ptr<float>(), top_p.data_ptr<float>(),
+                top_k.data_ptr<int>(),
                 (const long long*)seed.data_ptr<int64_t>(),
                 offset.data_ptr<int>(), up,
-                (long long*)out.data_ptr<int64_t>(), cur_stream());
+                (long long*)out.data_ptr<int64_t>(), op.stream);
   return out;
 }
 
 // Decode fast path: q [B,1,Hq,D] against the KV cache (flash-decoding
-// split-KV partials; no V transpose needed).
-std::vector<torch::Tensor> attn_decode(torch::Tensor q, torch::Tensor k,
-                                       torch::Tensor v, double scale,
-                                       c10::optional<torch::Tensor>
-                                           len_dev) {
-  check_bf16_contig(q, "q");
-  const int B = (int)q.size(0), Hq = (int)q.size(2), D = (int)q.size(3);
-  const int Skv = (int)k.size(1), Hkv = (int)k.size(2);
-  // accept KV-cache VIEWS (prefix of a preallocated cache): inner
-  // strides must be dense; the batch stride only matters for B > 1
-  auto dense_kv = [&](const torch::Tensor& t, const char* n) {
-    TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kBFloat16,
-                n, " must be bf16 GPU");
+// split-KV partials; no V transpose needed). k and v may be VIEWS (the
+// prefix of a preallocated cache): the inner strides must be dense, the
+// batch stride only matters for B > 1. The values inside len_dev (<= Skv)
+// are the caller's contract.
+std::vector<Tensor> attn_decode(Tensor q, Tensor k, Tensor v, double scale,
+                                OptTensor len_dev) {
+  const Op op("attn_decode", q, BF16, "q");
+  TORCH_CHECK(q.dim() == 4 && q.size(1) == 1,
+              "attn_decode: q must be [B,1,Hq,D] (decode path wants S == 1)");
+  const int B = i32(q.size(0)), Hq = i32(q.size(2)), D = i32(q.size(3));
+  TORCH_CHECK(D == 64 || D == 128, "attn_decode: D must be 64 or 128");
+  TORCH_CHECK(op.dev(k, BF16, "k").dim() == 4 && k.size(0) == B &&
+              k.size(3) == D, "attn_decode: k must be [B,Skv,Hkv,D]");
+  op.shape(op.dev(v, BF16, "v"), k.sizes(), "v");
+  const int Skv = i32(k.size(1)), Hkv = i32(k.size(2));
+  TORCH_CHECK(Skv >= 1 && Hkv >= 1 && Hq >= 1 && Hq % Hkv == 0,
+              "attn_decode: Skv >= 1, Hq % Hkv (GQA group)");
+  auto dense_kv = [&](const Tensor& t, const char* n) {
     TORCH_CHECK(t.stride(3) == 1 && t.stride(2) == D &&
-                t.stride(1) == (long)Hkv * D,
-                n, " must be s/h/d-dense");
-    if (B > 1) TORCH_CHECK(t.is_contiguous(), n, " batch>1 needs contig");
+                t.stride(1) == (long)Hkv * D, n, " must be s/h/d-dense");
+    if (B > 1) op.dense(t, BF16, n);
   };
   dense_kv(k, "k");
   dense_kv(v, "v");
-  TORCH_CHECK(q.size(1) == 1, "decode path wants S == 1");
-  TORCH_CHECK(D == 64 || D == 128, "D must be 64 or 128");
-  const int ns = attn_decode_nsplit(Skv);
-  auto part = torch::empty({(long)B * Hq, ns, D + 2},
-                           q.options().dtype(torch::kFloat));
+  op.aligned16("q, k, v", {q.data_ptr(), k.data_ptr(), v.data_ptr()});
+  const int* ld = op.opt<int>(len_dev, I32, "len_dev");
+  TORCH_CHECK(!ld || len_dev->numel() == 1 || len_dev->numel() == B,
+              "len_dev must be [1] or [B]");
+  const int len_stride = ld && len_dev->numel() > 1;
   auto o = torch::empty_like(q);
-  auto lse = torch::empty({B, Hq, 1}, q.options().dtype(torch::kFloat));
-  const int* ld = nullptr;
-  int len_stride = 0;
-  if (len_dev.has_value()) {
-    TORCH_CHECK(len_dev->scalar_type() == torch::kInt &&
-                len_dev->is_cuda(), "len_dev must be int32 on GPU");
-    ld = len_dev->data_ptr<int>();
-    len_stride = len_dev->numel() > 1;
-    if (len_stride)
-      TORCH_CHECK(len_dev->numel() == B, "len_dev must be [1] or [B]");
-  }
+  auto lse = torch::empty({B, Hq, 1}, q.options().dtype(F32));
+  if (B == 0) return {o, lse};
+  auto part = torch::empty({(long)B * Hq, attn_decode_nsplit(Skv), D + 2},
+                           lse.options());
   launch_attn_decode(q.data_ptr(), k.data_ptr(), v.data_ptr(), ld,
                      part.data_ptr<float>(), o.data_ptr(),
                      lse.data_ptr<float>(), B, Hq, Hkv, Skv, D,
-                     (float)scale, len_stride, cur_stream());
+                     (float)scale, len_stride, op.stream);
   return {o, lse};
 }
 
 // All BSHD, read in place: nothing is transposed on the host side.
-std::vector<torch::Tensor> attn_bwd(torch::Tensor q, torch::Tensor k,
-                                    torch::Tensor v, torch::Tensor o,
-                                    torch::Tensor dO, torch::Tensor lse,
-                                    bool causal, double scale,
-                                    c10::optional<torch::Tensor> doc_start,
-                                    c10::optional<torch::Tensor> doc_end) {
-  check_bf16_contig(q, "q");
-  check_bf16_contig(k, "k");
-  check_bf16_contig(v, "v");
-  auto dO_c = dO.contiguous();
-  const int B = (int)q.size(0), S = (int)q.size(1), Hq = (int)q.size(2),
-            D = (int)q.size(3);
-  const int Skv = (int)k.size(1), Hkv = (int)k.size(2);
-  check_bf16_contig(o, "o");
-  const int* dsp = doc_map_ptr(doc_start, B, S, "doc_start");
-  const int* dep = doc_map_ptr(doc_end, B, S, "doc_end");
+std::vector<Tensor> attn_bwd(Tensor q, Tensor k, Tensor v, Tensor o,
+                             Tensor dO, Tensor lse, bool causal,
+                             double scale, OptTensor doc_start,
+                             OptTensor doc_end) {
+  const Op op("attn_bwd", q, BF16, "q");
+  const AttnShape a = check_attn(op, q, k, v);
+  op.shape(op.dense(o, BF16, "o"), q.sizes(), "o");
+  op.shape(op.dev(dO, BF16, "dO"), q.sizes(), "dO");
+  auto dO_c = dO.contiguous();   // autograd may hand over a strided view
+  op.shape(op.dense(lse, F32, "lse"), {a.B, a.Hq, a.S}, "lse");
+  op.aligned16("o, dO", {o.data_ptr(), dO_c.data_ptr()});
+  const int* dsp = doc_map(op, doc_start, a.B, a.S, "doc_start");
+  const int* dep = doc_map(op, doc_end, a.B, a.S, "doc_end");
   TORCH_CHECK((dsp == nullptr) == (dep == nullptr),
               "doc_start and doc_end go together");
-  if (dsp) check_docs_shape(causal, S, Skv);
-  auto delta = torch::empty({B, Hq, S}, q.options().dtype(torch::kFloat));
+  if (dsp) check_docs_shape(causal, a.S, a.Skv);
   // dkdv and dq gather their B-fragments from the ROW-major LDS tiles
   // with ds_read_b64_tr_b16 (tr_bfrag) — no pre-transposed Q/K/dO
   // copies, no transpose_sd pre-passes in the backward at all
   auto dq = torch::empty_like(q);
   auto dk = torch::empty_like(k);
   auto dv = torch::empty_like(v);
+  if (a.B == 0) return {dq, dk, dv};
+  auto delta = torch::empty_like(lse);
   // dq goes first: its prologue forms delta = rowsum(dO o O) from the dO
   // fragments it holds and writes it; dkdv, next on the same stream,
   // reads it. There is no separate delta pass.
   launch_attn_bwd_dq(q.data_ptr(), k.data_ptr(), v.data_ptr(),
                      dO_c.data_ptr(), o.data_ptr(), lse.data_ptr<float>(),
-                     delta.data_ptr<float>(), dq.data_ptr(), dsp, B, Hq,
-                     Hkv, S, Skv, D, (float)scale, causal ? 1 : 0,
-                     cur_stream());
+                     delta.data_ptr<float>(), dq.data_ptr(), dsp, a.B, a.Hq,
+                     a.Hkv, a.S, a.Skv, a.D, (float)scale, causal ? 1 : 0,
+                     op.stream);
   launch_attn_bwd_dkdv(q.data_ptr(), k.data_ptr(), v.data_ptr(),
                        dO_c.data_ptr(), lse.data_ptr<float>(),
                        delta.data_ptr<float>(), dk.data_ptr(),
-                       dv.data_ptr(), dep, B, Hq, Hkv, S, Skv, D,
-                       (float)scale, causal ? 1 : 0, cur_stream());
+                       dv.data_ptr(), dep, a.B, a.Hq, a.Hkv, a.S, a.Skv,
+                       a.D, (float)scale, causal ? 1 : 0, op.stream);
   return {dq, dk, dv};
 }
 

@@ -4,6 +4,7 @@
 // stay in VGPRs (runtime-indexed ext_vector arrays spill to scratch).
 // Numerics contract: datatunerx_amd/ops/reference.py.
 #include "dtx_common.h"
+#include "dtx_launch.h"
 
 // ------------------------------------------------------------ RMSNorm fwd
 // x [M,H] bf16, w [H] bf16 -> y [M,H] bf16, inv [M] f32. One block per

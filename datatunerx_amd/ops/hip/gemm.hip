@@ -58,6 +58,7 @@
 // 16-B chunks only WITHIN one row's 64-B k-half, so global requests
 // still cover whole 64-B lines (no FETCH cost).
 #include "dtx_mfma.h"
+#include "dtx_launch.h"
 
 typedef __attribute__((ext_vector_type(4))) unsigned uint4v;
 typedef __attribute__((ext_vector_type(2))) unsigned uint2v;

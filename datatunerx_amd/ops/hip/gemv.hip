@@ -5,6 +5,7 @@
 // decode weights" row: no LDS round trip, deep unroll, late waits.
 // hipBLASLt's M=1 kernels leave ~3x on the table for these shapes.
 #include "dtx_common.h"
+#include "dtx_launch.h"
 
 __global__ __launch_bounds__(DTX_BLOCK)
 void gemv_bf16_kernel(const unsigned short* __restrict__ X,

@@ -16,6 +16,7 @@
 // R is a compile-time bound so accumulators stay in VGPRs (guide §5.4
 // rule 20).
 #include "dtx_mfma.h"
+#include "dtx_launch.h"
 
 // x (o mask) rounded to bf16, the operand every LoRA kernel contracts
 // MODE 1: bf16 mask fragment; MODE 2: fp32 mask values from the RNG
@@ -612,9 +613,6 @@ bool lora_expand_rng_ok(long M, int N, int r) {
 }
 
 // ------------------------------------------------------------- launchers
-void launch_reduce_partials(const float* part, float* out, int P, long L,
-                            hipStream_t s);
-
 void launch_dropout_mask(void* Mk, long n, unsigned long long seed,
                          float keep, hipStream_t s) {
   unsigned thr16; float ik;

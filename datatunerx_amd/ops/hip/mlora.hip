@@ -33,6 +33,7 @@
 // grids are shaped to spread one row's adapter (R*K*2 bytes) over many
 // waves rather than to reuse anything between rows.
 #include "dtx_common.h"
+#include "dtx_launch.h"
 
 template <int RJ>
 __global__ __launch_bounds__(DTX_BLOCK)

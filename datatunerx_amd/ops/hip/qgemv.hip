@@ -38,6 +38,7 @@
 // stored; lanes past K load nothing and feed zeros in BOTH operands;
 // batch rows >= M are zeros in registers. Row offsets are long.
 #include "dtx_mfma.h"
+#include "dtx_launch.h"
 
 typedef __attribute__((ext_vector_type(4))) unsigned uint4q;
 

@@ -5,6 +5,7 @@
 // (VERDICT r1 weak #3). Reference exercise: bitsandbytes
 // BitsAndBytesConfig, /root/reference/cmd/tuning/train.py:224-234.
 #include "dtx_common.h"
+#include "dtx_launch.h"
 
 // int8: q [N,K] int8 row-major, scale [N] f32 -> out [N,K] bf16.
 // Each thread handles 8 elements (two dwords of int8, one bf16x8 store).

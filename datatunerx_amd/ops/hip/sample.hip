@@ -25,6 +25,7 @@
 // false, so padding (and a NaN logit) is never a maximum, a candidate or
 // a member.
 #include "dtx_common.h"
+#include "dtx_launch.h"
 
 #define SAMPLE_THREADS 1024
 #define SAMPLE_WAVES (SAMPLE_THREADS / WAVE)

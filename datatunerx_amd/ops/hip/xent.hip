@@ -5,6 +5,7 @@
 // Replaces the HF loss path the reference uses (train.py:256-264 forces
 // an fp32 lm_head; here the reduction is fp32 while logits stay bf16).
 #include "dtx_common.h"
+#include "dtx_launch.h"
 
 __device__ __forceinline__ float block_reduce_max(float x, float* scratch) {
   const int lane = threadIdx.x & (WAVE - 1);
