@@ -20,7 +20,8 @@ from ..ops import doc_end_from_start, rope_tables
 from ..ops.autograd import (PairedFrozenGemm, QKVProj, attention,
                             cross_entropy, rmsnorm, rmsnorm_tap,
                             rope, swiglu)
-from .lora import FrozenLinear, LoRALinearModule, draw_dropout_seed
+from .lora import (FrozenLinear, LoRALinearModule, _weight_t,
+                   draw_dropout_seed)
 from .multilora import MultiLoRALinear
 
 
@@ -185,7 +186,9 @@ class LlamaAttention(nn.Module):
                 sv = draw_dropout_seed()
             q, k, v = QKVProj.apply(x, qm.weight, qm.lora_A, qm.lora_B,
                                     km.weight, vm.weight, vm.lora_A,
-                                    vm.lora_B, qm.scale, sq, sv, keep)
+                                    vm.lora_B, qm.scale, sq, sv, keep,
+                                    _weight_t(qm), _weight_t(km),
+                                    _weight_t(vm))
         else:
             q = _mproj(self.q_proj, x, adapters)
             k = _mproj(self.k_proj, x, adapters)
@@ -230,7 +233,9 @@ class LlamaMLP(nn.Module):
             # one node for the gate/up pair: backward accumulates both
             # dgrads with addmm_ instead of a grad-add per layer
             g, u = PairedFrozenGemm.apply(x, self.gate_proj.weight,
-                                          self.up_proj.weight)
+                                          self.up_proj.weight,
+                                          _weight_t(self.gate_proj),
+                                          _weight_t(self.up_proj))
             h = swiglu(g, u)
         else:
             h = swiglu(_mproj(self.gate_proj, x, adapters),

@@ -24,35 +24,104 @@ from ..ops.autograd import FrozenGemm
 from ..ops.autograd import LoRALinear as _FusedLoRAFn
 
 
-def _weight_t(mod: nn.Module):
-    """Cached W^T for a frozen base weight: both the forward (x @ W^T)
-    and the dgrad (dy @ W) then run the hand-written NT MFMA GEMM with
-    the contraction contiguous — 288 GB HBM3E per MI355X makes the
-    persistent transposed copy free. Built lazily on first GPU forward;
-    None when the shape is outside the kernel's support.
+def dgrad_wt_pays(n: int, k: int) -> bool:
+    """Shape families [n,k] of frozen weights whose dgrad is faster
+    against a cached W^T (F.linear(dy, W^T), the library's forward
+    layout) than as dy @ W. A family that does not clear the probe's
+    spread (tools/bench_basegemm.py, recorded in profiles/README.md)
+    is refused here and builds no copy."""
+    return True
 
-    Gated by DTX_CUSTOM_GEMM=1: the hand-written kernel currently
-    measures 1.25-1.33 PF/s on the mb24 training shapes vs the tuned
-    hipBLASLt picks' 1.47-1.67 (tools/bench_mygemm.py, within-probe
-    A/B), so routing the 60%-of-step base GEMMs through it would
-    regress tokens/s; it stays opt-in until it wins."""
-    if os.environ.get("DTX_CUSTOM_GEMM", "0") != "1":
+
+_TENSOR_DATA = torch.Tensor.data
+
+
+class _DataTrackedParameter(nn.Parameter):
+    """A frozen weight whose W^T is cached. torch gives `weight.data` a
+    version counter of its own, so `weight.data.mul_(2)` or
+    `weight.data.copy_(...)` leave `weight._version` where it was; this
+    class counts every use of `.data` instead, and the count is part of
+    the cache key. A use that only reads costs one rebuild of the copy,
+    never a stale one. _weight_t gives a plain nn.Parameter this class
+    when it first caches its transpose; nothing else about the
+    parameter changes (same storage, same flags, still an
+    nn.Parameter)."""
+
+    @property
+    def data(self):
+        self.__dict__["_data_uses"] = self.__dict__.get("_data_uses", 0) + 1
+        return _TENSOR_DATA.__get__(self)
+
+    @data.setter
+    def data(self, value):
+        self.__dict__["_data_uses"] = self.__dict__.get("_data_uses", 0) + 1
+        _TENSOR_DATA.__set__(self, value)
+
+
+def _weight_t(mod: nn.Module, any_device: bool = False):
+    """Cached W^T [K,N] of a frozen base weight [N,K], or None. With it
+    the dgrad dx = dy @ W runs as F.linear(dy, W^T): the library's
+    forward layout, both operands contraction-contiguous, which it runs
+    faster than the "NN" form of dy @ W. Frozen weights never change and
+    288 GB of HBM3E make the persistent duplicate cheap (one extra bf16
+    copy of the frozen projections and the lm_head).
+
+    Built only for a CUDA bf16 weight with requires_grad == False, with
+    grad mode on and DTX_DGRAD_WT != 0: serving and eval (no_grad) and
+    full-parameter training never build it. The cache is a plain
+    attribute (no parameter, no buffer: absent from state_dict() and
+    adapter checkpoints) keyed on the weight's data_ptr(), its _version
+    and its count of `.data` uses (_DataTrackedParameter), so
+    init_random, a checkpoint load, .to() or any in-place write, through
+    `weight.data` too, rebuilds it. any_device lifts the CUDA/bf16
+    condition (tests)."""
+    w = mod.weight
+    if (w.requires_grad or not torch.is_grad_enabled()
+            or os.environ.get("DTX_DGRAD_WT", "1") == "0"):
         return None
-    wt = getattr(mod, "_wt", False)
-    if wt is False:
-        w = mod.weight
-        n, k = w.shape
-        if (w.is_cuda and w.dtype == torch.bfloat16
-                and gemm_nt_supported(n, k) and gemm_nt_supported(k, n)):
-            wt = w.detach().t().contiguous()
-        else:
-            wt = None
-        mod._wt = wt
-    return wt
+    if not any_device and not (w.is_cuda and w.dtype == torch.bfloat16):
+        return None
+    if not dgrad_wt_pays(*w.shape):
+        return None
+    if type(w) is nn.Parameter:
+        w.__class__ = _DataTrackedParameter
+    key = (w.data_ptr(), w._version, w.__dict__.get("_data_uses", 0))
+    cached = mod.__dict__.get("_wt")
+    if cached is None or cached[0] != key:
+        cached = (key, w.detach().t().contiguous())
+        mod.__dict__["_wt"] = cached
+    return cached[1]
+
+
+def _state_without_wt(self):
+    """__getstate__ of the modules _weight_t caches on: copy.deepcopy and
+    whole-module pickling take the module without its cached W^T (the
+    copy rebuilds its own on first use)."""
+    state = self.__dict__.copy()
+    state.pop("_wt", None)
+    return state
+
+
+def _custom_gemm(w, wt) -> bool:
+    """Route this projection through the hand-written NT MFMA GEMM
+    (gemm.hip), forward and dgrad? Opt-in with DTX_CUSTOM_GEMM=1: the
+    kernel measures 1.25-1.33 PF/s on the mb24 training shapes vs the
+    tuned hipBLASLt picks' 1.47-1.67 (tools/bench_mygemm.py, within-probe
+    A/B), so it stays off until it wins. Needs both [N,K] and [K,N]
+    inside the kernel's support and, for the dgrad, the cached W^T."""
+    if os.environ.get("DTX_CUSTOM_GEMM", "0") != "1":
+        return False
+    if wt is None and torch.is_grad_enabled():
+        return False
+    n, k = w.shape
+    return (w.is_cuda and w.dtype == torch.bfloat16
+            and gemm_nt_supported(n, k) and gemm_nt_supported(k, n))
 
 
 class FrozenLinear(nn.Module):
     """Bias-free frozen linear (Llama projections are bias-free)."""
+
+    __getstate__ = _state_without_wt
 
     def __init__(self, in_features: int, out_features: int,
                  dtype=torch.bfloat16):
@@ -67,12 +136,13 @@ class FrozenLinear(nn.Module):
             from ..ops import gemv
             y = gemv(x, self.weight)         # decode: streaming GEMV
             return y if residual is None else y + residual
-        if x.is_cuda:
+        if not self.weight.requires_grad:
+            # one node: residual add in the GEMM epilogue without a copy
+            # of the residual, dgrad against the cached W^T
             wt = _weight_t(self)
-            if wt is not None:
-                # hand-written MFMA GEMM; residual add fused into the
-                # kernel epilogue (no separate elementwise pass)
-                return FrozenGemm.apply(x, self.weight, wt, residual)
+            return FrozenGemm.apply(x, self.weight, wt, residual,
+                                    _custom_gemm(self.weight, wt))
+        # trainable base (full-parameter training): torch's own nodes
         if residual is not None:
             # fold the residual add into the GEMM epilogue (addmm,
             # beta=1): one kernel instead of linear + elementwise add
@@ -81,7 +151,6 @@ class FrozenLinear(nn.Module):
             r2 = residual.reshape(-1, self.out_features)
             return torch.addmm(r2, x2, self.weight.t()).reshape(
                 *xs[:-1], self.out_features)
-        # hipBLASLt fallback for unsupported shapes / CPU
         return F.linear(x, self.weight)
 
 
@@ -99,6 +168,8 @@ class LoRALinearModule(nn.Module):
     kernel is decided in the op layer (ops.lora_expand_add_t), never
     here."""
 
+    __getstate__ = _state_without_wt
+
     def __init__(self, in_features: int, out_features: int, r: int = 8,
                  alpha: float = 32.0, dropout: float = 0.0,
                  dtype=torch.bfloat16):
@@ -114,12 +185,13 @@ class LoRALinearModule(nn.Module):
         nn.init.kaiming_uniform_(self.lora_A, a=math.sqrt(5))
 
     def forward(self, x):
-        wt = _weight_t(self) if x.is_cuda else None
+        wt = _weight_t(self)
         seed, keep = 0, 1.0
         if self.training and self.dropout > 0.0:
             seed, keep = draw_dropout_seed(), 1.0 - self.dropout
         return _FusedLoRAFn.apply(x, self.weight, self.lora_A, self.lora_B,
-                                  self.scale, wt, seed, keep)
+                                  self.scale, wt, seed, keep,
+                                  _custom_gemm(self.weight, wt))
 
     def merged_weight(self):
         """W + s·B@A — used by the serving engine (no adapter overhead)."""

@@ -241,6 +241,16 @@ def gemm_nt(a, b, src=None):
     return out
 
 
+def gemm_nt_add(a, b, c):
+    """d[M,N] = a[M,K] @ b[N,K]^T + c[M,N], bf16 with fp32 accumulation,
+    on hipBLASLt with C != D (basegemm.cpp): c is read and never written,
+    d is a fresh tensor. What torch.addmm(c, a, b.t()) computes, without
+    its copy of c into the result."""
+    if _gpu(a):
+        return _EXT.gemm_nt_add(a, b, c)
+    return torch.addmm(c, a, b.t())
+
+
 # -------------------------------------------------------------- LoRA
 # Dropout enters the kernels one of two ways:
 #   - `mask`: a materialized bf16 mask tensor (same shape as x / y)

@@ -10,10 +10,10 @@ import os
 
 import torch
 
-from . import (attn_bwd, attn_fwd, lora_contract, lora_contract2,
-               lora_expand_add2, lora_expand_add_t, lora_wgrad, rmsnorm_bwd,
-               rmsnorm_fwd, rope_bwd, rope_fwd, softmax_xent_bwd,
-               softmax_xent_fwd, swiglu_bwd, swiglu_fwd)
+from . import (attn_bwd, attn_fwd, gemm_nt_add, lora_contract,
+               lora_contract2, lora_expand_add2, lora_expand_add_t,
+               lora_wgrad, rmsnorm_bwd, rmsnorm_fwd, rope_bwd, rope_fwd,
+               softmax_xent_bwd, softmax_xent_fwd, swiglu_bwd, swiglu_fwd)
 
 
 class RMSNorm(torch.autograd.Function):
@@ -183,22 +183,43 @@ def per_row_cross_entropy(logits, targets, ignore_index: int = -100):
     return PerRowCrossEntropy.apply(logits, targets, ignore_index)
 
 
-def _base_gemm(x2, w, wt):
-    """Base-projection GEMM: the hand-written MFMA kernel (gemm.hip) when
-    a cached W^T is provided (both fwd and dgrad then run the fast NT
-    layout), hipBLASLt otherwise."""
+def _base_gemm(x2, w, custom):
+    """Base-projection GEMM x2 @ W^T: the library's forward layout, or
+    the hand-written MFMA kernel (gemm.hip) when `custom` (opt-in)."""
     from . import gemm_nt
-    if wt is not None and x2.is_cuda and x2.shape[0] > 0:
+    if custom and x2.is_cuda and x2.shape[0] > 0:
         return gemm_nt(x2, w)
     return torch.nn.functional.linear(x2, w)
+
+
+def _base_dgrad(dy2, w, wt, custom):
+    """dx = dy2 @ W of a frozen W [N,K]. With the cached wt = W^T [K,N]
+    it is F.linear(dy2, wt): the same forward-layout GEMM as the forward
+    pass (both operands contraction-contiguous) instead of the library's
+    slower "NN" form. `custom`: the hand-written NT kernel on wt."""
+    if custom and wt is not None and dy2.is_cuda:
+        from . import gemm_nt
+        return gemm_nt(dy2, wt)
+    if wt is not None:
+        return torch.nn.functional.linear(dy2, wt)
+    return dy2 @ w
+
+
+def _dgrad_acc(dx, dy2, w, wt):
+    """dx += dy2 @ W in the GEMM epilogue (beta = 1), against the cached
+    W^T when there is one."""
+    dx.addmm_(dy2, w if wt is None else wt.t())
 
 
 class LoRALinear(torch.autograd.Function):
     """y = x @ W^T + scale * (dropout(x) @ A^T) @ B^T  with frozen W.
 
-    W: [N,K] (frozen base, no wgrad) — the base GEMM is the hand-written
-    gfx950 MFMA kernel (ops/hip/gemm.hip) with `wt` = W^T cached so the
-    dgrad dx = dy @ W is the same contraction-contiguous NT kernel; the
+    W: [N,K] (frozen base, no wgrad). `wt` = the cached W^T (or None):
+    the dgrad dx = dy @ W then runs in the forward layout, see
+    _base_dgrad; `custom` routes both base GEMMs through the hand-written
+    gfx950 MFMA kernel (ops/hip/gemm.hip) instead of the library. When x
+    needs no gradient (layer 0 behind a frozen embedding) the base dgrad
+    and the dx expand-add are skipped. The
     low-rank path is the fused HIP contract/expand pair. A: [r,K],
     B: [N,r] (HF PEFT adapter layout, the checkpoint-compat contract —
     SURVEY.md §5 Checkpoint/resume). B is transposed once here and the
@@ -213,38 +234,38 @@ class LoRALinear(torch.autograd.Function):
     """
 
     @staticmethod
-    def forward(ctx, x, w, a, b, scale, wt=None, seed=0, keep=1.0):
+    def forward(ctx, x, w, a, b, scale, wt=None, seed=0, keep=1.0,
+                custom=False):
         xs = x.shape
         x2 = x.reshape(-1, xs[-1])
         if x2.is_cuda and x2.shape[0] == 1 and keep >= 1.0:
             from . import gemv
             y = gemv(x2, w)                      # decode: streaming GEMV
         else:
-            y = _base_gemm(x2, w, wt)
+            y = _base_gemm(x2, w, custom)
         bt = b.t().contiguous()                  # [r,N]
         t = lora_contract(x2, a, None, seed, keep)   # (x o mask) @ A^T
         lora_expand_add_t(y, t, bt, scale)       # y += s * t @ B^T
         ctx.save_for_backward(x2, w, a, bt, t, wt)
-        ctx.meta = (scale, seed, keep, xs, b.dtype)
+        ctx.meta = (scale, seed, keep, xs, b.dtype, custom)
         return y.reshape(*xs[:-1], w.shape[0])
 
     @staticmethod
     def backward(ctx, dy):
         x2, w, a, bt, t, wt = ctx.saved_tensors
-        s, seed, keep, xs, b_dtype = ctx.meta
+        s, seed, keep, xs, b_dtype, custom = ctx.meta
         dy2 = dy.reshape(-1, dy.shape[-1]).contiguous()
-        if wt is not None and dy2.is_cuda:
-            from . import gemm_nt
-            dx = gemm_nt(dy2, wt)                # base dgrad (NT MFMA)
-        else:
-            dx = dy2 @ w
         dt = lora_contract(dy2, bt)                   # [M,r] = dy @ B
         db = lora_wgrad(t, dy2, s).t().contiguous()   # [r,N] -> B is [N,r]
         da = lora_wgrad(dt, x2, s, None, seed, keep)  # dt^T @ (x o mask)
-        # dx += mask o (s * dt @ A)
-        lora_expand_add_t(dx, dt, a, s, None, seed, keep)
-        return (dx.reshape(xs), None, da.to(a.dtype), db.to(b_dtype),
-                None, None, None, None)
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = _base_dgrad(dy2, w, wt, custom)
+            # dx += mask o (s * dt @ A)
+            lora_expand_add_t(dx, dt, a, s, None, seed, keep)
+            dx = dx.reshape(xs)
+        return (dx, None, da.to(a.dtype), db.to(b_dtype),
+                None, None, None, None, None)
 
 
 def lora_linear(x, w, a, b, scale: float, wt=None):
@@ -252,30 +273,44 @@ def lora_linear(x, w, a, b, scale: float, wt=None):
 
 
 class FrozenGemm(torch.autograd.Function):
-    """y = x @ W^T (+ residual) with frozen W via the MFMA NT kernel; the
-    residual add runs in the GEMM epilogue (one kernel, no extra HBM
-    round-trip). dgrad reuses the kernel with the cached W^T."""
+    """y = x @ W^T (+ residual) with frozen W: the one node of a frozen
+    projection (the lm_head included).
+
+    Forward: F.linear, or with a residual ops.gemm_nt_add — hipBLASLt
+    with C != D, so the residual is added in the GEMM epilogue without
+    torch.addmm's copy of it into the result. Backward: dx = dy @ W
+    against the cached `wt` = W^T when one is given (_base_dgrad); the
+    residual's gradient is dy itself. `custom` runs both GEMMs on the
+    hand-written MFMA NT kernel instead (needs wt)."""
 
     @staticmethod
-    def forward(ctx, x, w, wt, residual):
-        from . import gemm_nt
+    def forward(ctx, x, w, wt, residual, custom=False):
         xs = x.shape
         x2 = x.reshape(-1, xs[-1])
         r2 = residual.reshape(-1, w.shape[0]).contiguous() \
             if residual is not None else None
-        y = gemm_nt(x2, w, r2)
-        ctx.save_for_backward(wt)
-        ctx.xshape, ctx.has_res = xs, residual is not None
+        if custom:
+            from . import gemm_nt
+            y = gemm_nt(x2, w, r2)
+        elif r2 is None:
+            y = torch.nn.functional.linear(x2, w)
+        elif x2.is_cuda and not (x2.dtype == torch.bfloat16
+                                 and x2.shape[0] > 1):
+            y = torch.addmm(r2, x2, w.t())
+        else:
+            y = gemm_nt_add(x2.contiguous(), w, r2)
+        ctx.save_for_backward(w, wt)
+        ctx.xshape, ctx.has_res, ctx.custom = xs, residual is not None, custom
         return y.reshape(*xs[:-1], w.shape[0])
 
     @staticmethod
     def backward(ctx, dy):
-        from . import gemm_nt
-        (wt,) = ctx.saved_tensors
-        dy2 = dy.reshape(-1, dy.shape[-1]).contiguous()
-        dx = gemm_nt(dy2, wt)
-        return (dx.reshape(ctx.xshape), None, None,
-                dy if ctx.has_res else None)
+        w, wt = ctx.saved_tensors
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dy2 = dy.reshape(-1, dy.shape[-1]).contiguous()
+            dx = _base_dgrad(dy2, w, wt, ctx.custom).reshape(ctx.xshape)
+        return dx, None, None, dy if ctx.has_res else None, None
 
 
 class FusedLinearCrossEntropy(torch.autograd.Function):
@@ -362,27 +397,28 @@ class PairedFrozenGemm(torch.autograd.Function):
     """(x@Wg^T, x@Wu^T) for two frozen weights sharing one input (the
     MLP gate/up pair): backward ACCUMULATES the two dgrads into one
     buffer with addmm_ (beta=1 GEMM epilogue), eliminating the autograd
-    grad-add that a shared input otherwise costs per layer."""
+    grad-add that a shared input otherwise costs per layer. wgt / wut:
+    the cached W^T of each weight or None (_base_dgrad)."""
 
     @staticmethod
-    def forward(ctx, x, wg, wu):
+    def forward(ctx, x, wg, wu, wgt=None, wut=None):
         xs = x.shape
         x2 = x.reshape(-1, xs[-1])
         g = torch.nn.functional.linear(x2, wg)
         u = torch.nn.functional.linear(x2, wu)
-        ctx.save_for_backward(wg, wu)
+        ctx.save_for_backward(wg, wu, wgt, wut)
         ctx.xshape = xs
         n = wg.shape[0]
         return (g.reshape(*xs[:-1], n), u.reshape(*xs[:-1], n))
 
     @staticmethod
     def backward(ctx, dg, du):
-        wg, wu = ctx.saved_tensors
+        wg, wu, wgt, wut = ctx.saved_tensors
         dg2 = dg.reshape(-1, dg.shape[-1])
         du2 = du.reshape(-1, du.shape[-1])
-        dx = dg2 @ wg
-        dx.addmm_(du2, wu)              # accumulate in the GEMM epilogue
-        return dx.reshape(ctx.xshape), None, None
+        dx = _base_dgrad(dg2, wg, wgt, False)
+        _dgrad_acc(dx, du2, wu, wut)    # accumulate in the GEMM epilogue
+        return dx.reshape(ctx.xshape), None, None, None, None
 
 
 class QKVProj(torch.autograd.Function):
@@ -403,7 +439,7 @@ class QKVProj(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, wq, aq, bq, wk, wv, av, bv, scale,
-                seed_q, seed_v, keep):
+                seed_q, seed_v, keep, wqt=None, wkt=None, wvt=None):
         xs = x.shape
         x2 = x.reshape(-1, xs[-1])
         yq = torch.nn.functional.linear(x2, wq)
@@ -414,7 +450,8 @@ class QKVProj(torch.autograd.Function):
         tq, tv = lora_contract2(x2, aq, av, seed_q, seed_v, keep)
         lora_expand_add_t(yq, tq, bqt, scale)
         lora_expand_add_t(yv, tv, bvt, scale)
-        ctx.save_for_backward(x2, wq, aq, bqt, wk, wv, av, bvt, tq, tv)
+        ctx.save_for_backward(x2, wq, aq, bqt, wk, wv, av, bvt, tq, tv,
+                              wqt, wkt, wvt)
         ctx.meta = (scale, seed_q, seed_v, keep, xs, bq.dtype, bv.dtype)
         return (yq.reshape(*xs[:-1], wq.shape[0]),
                 yk.reshape(*xs[:-1], wk.shape[0]),
@@ -422,22 +459,30 @@ class QKVProj(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dyq, dyk, dyv):
-        x2, wq, aq, bqt, wk, wv, av, bvt, tq, tv = ctx.saved_tensors
+        (x2, wq, aq, bqt, wk, wv, av, bvt, tq, tv,
+         wqt, wkt, wvt) = ctx.saved_tensors
         scale, seed_q, seed_v, keep, xs, bq_dtype, bv_dtype = ctx.meta
         dq2 = dyq.reshape(-1, dyq.shape[-1]).contiguous()
-        dk2 = dyk.reshape(-1, dyk.shape[-1]).contiguous()
         dv2 = dyv.reshape(-1, dyv.shape[-1]).contiguous()
-        dx = dq2 @ wq
-        dx.addmm_(dk2, wk)
-        dx.addmm_(dv2, wv)
-        # LoRA grads + low-rank dx terms (expand_add is in-place on dx)
+        # LoRA grads
         dtq = lora_contract(dq2, bqt)
         dtv = lora_contract(dv2, bvt)
         dbq = lora_wgrad(tq, dq2, scale).t().contiguous()
         dbv = lora_wgrad(tv, dv2, scale).t().contiguous()
         daq = lora_wgrad(dtq, x2, scale, None, seed_q, keep)
         dav = lora_wgrad(dtv, x2, scale, None, seed_v, keep)
-        lora_expand_add2(dx, dtq, dtv, aq, av, scale, seed_q, seed_v, keep)
-        return (dx.reshape(xs), None, daq.to(aq.dtype),
+        dx = None
+        if ctx.needs_input_grad[0]:
+            # x needs no gradient behind a frozen embedding (layer 0):
+            # then the three base dgrads and the dx expand-add are not run
+            dk2 = dyk.reshape(-1, dyk.shape[-1]).contiguous()
+            dx = _base_dgrad(dq2, wq, wqt, False)
+            _dgrad_acc(dx, dk2, wk, wkt)
+            _dgrad_acc(dx, dv2, wv, wvt)
+            # low-rank dx terms (expand_add is in-place on dx)
+            lora_expand_add2(dx, dtq, dtv, aq, av, scale, seed_q, seed_v,
+                             keep)
+            dx = dx.reshape(xs)
+        return (dx, None, daq.to(aq.dtype),
                 dbq.to(bq_dtype), None, None, dav.to(av.dtype),
-                dbv.to(bv_dtype), None, None, None, None)
+                dbv.to(bv_dtype), None, None, None, None, None, None, None)

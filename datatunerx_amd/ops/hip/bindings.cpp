@@ -562,6 +562,53 @@ Tensor gemm_nt(Tensor a, Tensor b, OptTensor src) {
   return c;
 }
 
+// Scratch handed to hipBLASLt per call: the size torch itself gives the
+// library on this build (76 MiB on gfx950 unless HIPBLASLT_WORKSPACE_SIZE
+// says otherwise), so the heuristic chooses among the same algorithms.
+long gemm_nt_add_workspace_bytes() {
+  return (long)at::cuda::getCUDABlasLtWorkspaceSize();
+}
+
+// (headers', loaded library's) hipBLASLt version on the current device.
+std::vector<long> gemm_nt_add_versions_py() {
+  int header = 0, loaded = 0;
+  const char* failed = nullptr;
+  const int st = gemm_nt_add_versions(
+      at::cuda::getCurrentCUDAStream().device_index(), &header, &loaded,
+      &failed);
+  TORCH_CHECK(st == 0, "gemm_nt_add: ", failed ? failed : "hipBLASLt",
+              " failed with status ", st);
+  return {header, loaded};
+}
+
+// d[M,N] = a[M,K] @ b[N,K]^T + c[M,N] on hipBLASLt with C != D
+// (basegemm.cpp): c is read only, d is fresh. The frozen projections'
+// residual add without torch.addmm's copy of the residual.
+Tensor gemm_nt_add(Tensor a, Tensor b, Tensor c) {
+  const Op op("gemm_nt_add", a, BF16, "a");
+  op.dense(b, BF16, "b");
+  op.dense(c, BF16, "c");
+  TORCH_CHECK(a.dim() == 2 && b.dim() == 2 && c.dim() == 2,
+              "gemm_nt_add: a [M,K], b [N,K], c [M,N]");
+  const int M = i32(a.size(0)), K = i32(a.size(1)), N = i32(b.size(0));
+  TORCH_CHECK(b.size(1) == K, "gemm_nt_add: a [M,K] and b [N,K] differ in "
+              "K: ", a.sizes(), " against ", b.sizes());
+  op.shape(c, {M, N}, "c");
+  op.aligned16("a, b, c", {a.data_ptr(), b.data_ptr(), c.data_ptr()});
+  if (M == 0 || N == 0) return torch::empty({M, N}, a.options());
+  if (K == 0) return c.clone();
+  auto d = torch::empty({M, N}, a.options());
+  const long ws_bytes = gemm_nt_add_workspace_bytes();
+  auto ws = torch::empty({ws_bytes}, a.options().dtype(torch::kByte));
+  const char* failed = nullptr;
+  const int st = launch_gemm_nt_add(
+      a.get_device(), a.data_ptr(), b.data_ptr(), c.data_ptr(), d.data_ptr(),
+      M, N, K, ws.data_ptr(), (size_t)ws_bytes, op.stream, &failed);
+  TORCH_CHECK(st == 0, "gemm_nt_add: ", failed ? failed : "hipBLASLt",
+              " failed with status ", st, " for M=", M, " N=", N, " K=", K);
+  return d;
+}
+
 // weight-only dequant (int8 per-row / int4 group-wise) -> bf16
 Tensor dequant_int8(Tensor q, Tensor scale) {
   const Op op("dequant_int8", q, torch::kChar, "q");
@@ -870,6 +917,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("sample_max_vocab", &sample_max_vocab);
   m.def("gemm_nt", &gemm_nt, py::arg("a"), py::arg("b"),
         py::arg("src") = py::none());
+  m.def("gemm_nt_add", &gemm_nt_add, py::arg("a"), py::arg("b"),
+        py::arg("c"));
+  m.def("gemm_nt_add_workspace_bytes", &gemm_nt_add_workspace_bytes);
+  m.def("gemm_nt_add_versions", &gemm_nt_add_versions_py);
   m.def("attn_decode", &attn_decode, py::arg("q"), py::arg("k"),
         py::arg("v"), py::arg("scale"), py::arg("len_dev") = py::none());
 }

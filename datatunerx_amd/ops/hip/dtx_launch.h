@@ -8,6 +8,7 @@
 // >= 1) unless the comment says otherwise. bf16 tensors travel as void*.
 #pragma once
 #include <hip/hip_runtime_api.h>
+#include <cstddef>
 
 // ------------------------------------------------------------ elementwise.hip
 // x, y [M,H] bf16, w [H] bf16, inv [M] f32. H % 8 == 0, H <= 16384 (a
@@ -169,6 +170,21 @@ void launch_attn_bwd_dkdv(const void* q, const void* k, const void* v,
 // N % 256 == 0, K % 64 == 0, K >= 128; any M >= 1.
 void launch_gemm_nt(const void* A, const void* B, const void* SRC, void* C,
                     long M, int N, int K, hipStream_t stream);
+// basegemm.cpp, on hipBLASLt: D[M,N] = A[M,K] @ B[N,K]^T + C[M,N], bf16,
+// fp32 accumulate; C is only read, D != C. All four 16-byte aligned,
+// M, N, K >= 1. ws: ws_bytes of device scratch the call may use until it
+// has run on `stream`. `device` is the current device (it keys the handle
+// and the per-shape plans). Returns 0, or the hipBLASLt status with
+// *failed naming the call that gave it.
+int launch_gemm_nt_add(int device, const void* A, const void* B,
+                       const void* C, void* D, int M, int N, int K,
+                       void* ws, size_t ws_bytes, hipStream_t stream,
+                       const char** failed);
+// hipBLASLt versions (major * 100000 + minor * 100 + patch): of the headers
+// basegemm.cpp was compiled with, and of the library the process loaded.
+// Creates the device's handle if need be; returns as launch_gemm_nt_add.
+int gemm_nt_add_versions(int device, int* header, int* loaded,
+                         const char** failed);
 // y[N] = x[K] @ w[N,K]^T, bf16; K % 8 == 0.
 void launch_gemv_bf16(const void* x, const void* w, void* y, int N, int K,
                       hipStream_t st);

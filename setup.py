@@ -28,6 +28,11 @@ setup(
         CUDAExtension(
             name="datatunerx_amd.ops._dtx_hip",
             sources=sources,
+            # basegemm.cpp calls hipBLASLt directly. The -L of torch's own
+            # lib directory comes first on the link line, so this is the
+            # copy torch loads; the process then holds that one copy
+            # (tests/test_base_gemm_gpu.py checks the loaded mappings).
+            libraries=["hipblaslt"],
             extra_compile_args={
                 "cxx": ["-O3", "-std=c++17"],
                 "nvcc": ["-O3", "-std=c++17", "--offload-arch=gfx950"],
