@@ -16,7 +16,7 @@ from dataclasses import dataclass
 import torch
 import torch.nn as nn
 
-from ..ops import doc_end_from_start, rope_tables
+from ..ops import KV8, attn_decode_q8, doc_end_from_start, rope_tables
 from ..ops.autograd import (PairedFrozenGemm, QKVProj, attention,
                             cross_entropy, rmsnorm, rmsnorm_tap,
                             rope, swiglu)
@@ -208,8 +208,12 @@ class LlamaAttention(nn.Module):
         len_dev = None
         if kv_cache is not None:
             k, v, len_dev = kv_cache.update(k, v)   # serving path (BSHD)
-        o = attention(q, k, v, causal=True, len_dev=len_dev,
-                      doc_start=doc_start, doc_end=doc_end)
+        if type(k) is KV8:       # int8 cache, decode step: k is its handle
+            o, _ = attn_decode_q8(q.contiguous(), k.k8, k.v8, k.ks, k.vs,
+                                  len_dev=len_dev, length=k.length)
+        else:
+            o = attention(q, k, v, causal=True, len_dev=len_dev,
+                          doc_start=doc_start, doc_end=doc_end)
         o = o.reshape(B, S, H * D)
         if residual is not None and isinstance(self.o_proj, FrozenLinear):
             return self.o_proj(o, residual)   # residual in GEMM epilogue

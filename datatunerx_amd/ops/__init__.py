@@ -10,6 +10,7 @@ PyTorch. CPU tensors always use the fp32 torch reference implementations
 from __future__ import annotations
 
 import os
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -215,6 +216,74 @@ def attn_bwd(q, k, v, o, do, lse, causal: bool = True,
     if _gpu(q):
         return _EXT.attn_bwd(q, k, v, o, do, lse, causal, scale)
     return ref.attn_bwd(q, k, v, o, do, lse, causal, scale)
+
+
+# ------------------------------------------------------ int8 KV cache
+class KV8(NamedTuple):
+    """An int8 KV cache as attn_decode_q8 takes it: k8, v8
+    [Bc,max_s,Hkv,D] int8, ks, vs [Bc,Hkv,max_s] f32, and the host-side
+    live length (None: len_dev, or the capacity)."""
+    k8: torch.Tensor
+    v8: torch.Tensor
+    ks: torch.Tensor
+    vs: torch.Tensor
+    length: Optional[int] = None
+
+
+def kv_int8_supported(Hq: int, Hkv: int, D: int) -> bool:
+    """Head shapes the int8 KV kernels take (kvq.hip): head_dim 64 or 128
+    and a GQA group of at most 16 query heads per kv head."""
+    return (D in (64, 128) and Hkv >= 1 and Hq >= 1 and Hq % Hkv == 0
+            and Hq // Hkv <= 16)
+
+
+def kv_quant_append(k, v, k8, v8, ks, vs, start: int = 0, wpos=None):
+    """Quantize k, v [B,S,Hkv,D] row by row (models/quant.py's per-row
+    absmax int8) into the cache k8, v8 [Bc,max_s,Hkv,D] int8 with scales
+    ks, vs [Bc,Hkv,max_s] f32. Row (b, s) goes to slot (b, start + s); with
+    wpos (int64 [B], S == 1) row b goes to the flat slot wpos[b] of
+    [Bc * max_s], read on the device (no host sync: hipGraph-capturable),
+    and a slot outside the cache is skipped."""
+    if _gpu(k):
+        _EXT.kv_quant_append(k, v, k8, v8, ks, vs, start, wpos)
+        return
+    B, S = k.shape[:2]
+    if wpos is not None and S != 1:
+        raise ValueError("kv_quant_append: wpos needs S == 1")
+    if B > k8.shape[0] or (wpos is None and
+                           not 0 <= start <= k8.shape[1] - S):
+        raise ValueError(f"kv_quant_append: rows {start}..{start + S} of "
+                         f"{B} batch rows do not fit the cache "
+                         f"{tuple(k8.shape)}")
+    ref.kv_quant_append(k, v, k8, v8, ks, vs, start, wpos)
+
+
+def attn_decode_q8(q, k8, v8, ks, vs, scale: float | None = None,
+                   len_dev=None, length: int | None = None):
+    """Decode attention of q [B,1,Hq,D] over an int8 KV cache (see
+    kv_quant_append) -> (o [B,1,Hq,D], lse [B,Hq,1]). The live length of
+    batch row b is len_dev (int32 [1] or [B], read on the device), else
+    `length`, else the capacity. All query heads of a GQA group share
+    one pass over the cache; needs kv_int8_supported(Hq, Hkv, D)."""
+    if scale is None:
+        scale = 1.0 / (q.shape[-1] ** 0.5)
+    if _gpu(q):
+        return _EXT.attn_decode_q8(q, k8, v8, ks, vs, scale, len_dev, length)
+    B, Hq, D = q.shape[0], q.shape[2], q.shape[3]
+    if not kv_int8_supported(Hq, k8.shape[2], D):
+        raise ValueError(f"attn_decode_q8: Hq={Hq} Hkv={k8.shape[2]} D={D} "
+                         "is outside the kernel contract "
+                         "(see kv_int8_supported)")
+    if len_dev is not None and length is not None:
+        raise ValueError("attn_decode_q8: give len_dev or length, not both")
+    if len_dev is not None:
+        if len_dev.numel() not in (1, B):
+            raise ValueError("attn_decode_q8: len_dev must be [1] or [B]")
+        lens = [min(int(n), k8.shape[1])
+                for n in len_dev.expand(B).tolist()]
+    else:
+        lens = [k8.shape[1] if length is None else int(length)] * B
+    return ref.attn_decode_q8(q, k8, v8, ks, vs, scale, lens)
 
 
 def gemv(x, w):

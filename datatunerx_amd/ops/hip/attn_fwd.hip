@@ -574,3 +574,15 @@ void launch_attn_decode(const void* q, const void* k, const void* v,
         part, (unsigned short*)o, lse, B, Hq, ns);
   }
 }
+
+// The combine alone, for kvq.hip's decode kernel: same kernel, same launch
+// shape as above.
+void launch_attn_decode_combine(const float* part, void* o, float* lse,
+                                int BH, int NS, int D, hipStream_t st) {
+  if (D == 128)
+    attn_decode_combine_kernel<128><<<BH, 64, 0, st>>>(
+        part, (unsigned short*)o, lse, BH, 1, NS);
+  else if (D == 64)
+    attn_decode_combine_kernel<64><<<BH, 64, 0, st>>>(
+        part, (unsigned short*)o, lse, BH, 1, NS);
+}

@@ -815,6 +815,101 @@ std::vector<Tensor> attn_decode(Tensor q, Tensor k, Tensor v, double scale,
   return {o, lse};
 }
 
+// ------------------------------------------------------ int8 KV cache
+// k8, v8 [Bc, max_s, Hkv, D] int8 and ks, vs [Bc, Hkv, max_s] f32
+// (kvq.hip): the cache's shape, D in {64, 128}.
+struct KvqShape { long Bc; int max_s, Hkv, D; };
+
+KvqShape check_kvq(const Op& op, const Tensor& k8, const Tensor& v8,
+                   const Tensor& ks, const Tensor& vs) {
+  op.dense(k8, torch::kChar, "k8");
+  TORCH_CHECK(k8.dim() == 4, op.op, ": k8 must be [Bc,max_s,Hkv,D]");
+  const KvqShape c{k8.size(0), i32(k8.size(1)), i32(k8.size(2)),
+                   i32(k8.size(3))};
+  TORCH_CHECK(c.D == 64 || c.D == 128, op.op, ": D must be 64 or 128");
+  TORCH_CHECK(c.max_s >= 1 && c.Hkv >= 1, op.op, ": max_s, Hkv >= 1");
+  op.shape(op.dense(v8, torch::kChar, "v8"), k8.sizes(), "v8");
+  op.shape(op.dense(ks, F32, "ks"), {c.Bc, c.Hkv, c.max_s}, "ks");
+  op.shape(op.dense(vs, F32, "vs"), {c.Bc, c.Hkv, c.max_s}, "vs");
+  op.aligned16("k8, v8", {k8.data_ptr(), v8.data_ptr()});
+  return c;
+}
+
+// Quantize k, v [B,S,Hkv,D] row by row into the cache. Without wpos row
+// (b, s) goes to slot (b, start + s); with wpos (int64 [B], S == 1) row b
+// goes to the flat slot wpos[b], read by the kernel only, which skips a
+// value outside the cache. No allocation: hipGraph-capturable.
+void kv_quant_append(Tensor k, Tensor v, Tensor k8, Tensor v8, Tensor ks,
+                     Tensor vs, long start, OptTensor wpos) {
+  const Op op("kv_quant_append", k, BF16, "k");
+  const KvqShape c = check_kvq(op, k8, v8, ks, vs);
+  TORCH_CHECK(k.dim() == 4 && k.size(2) == c.Hkv && k.size(3) == c.D,
+              "kv_quant_append: k must be [B,S,", c.Hkv, ",", c.D, "], got ",
+              k.sizes());
+  op.shape(op.dense(v, BF16, "v"), k.sizes(), "v");
+  const long B = k.size(0);
+  const int S = i32(k.size(1));
+  TORCH_CHECK(B <= c.Bc, "kv_quant_append: B = ", B, " rows for a cache of ",
+              c.Bc);
+  const long long* wp =
+      (const long long*)op.opt<int64_t>(wpos, I64, "wpos", B);
+  if (wp) {
+    TORCH_CHECK(S == 1, "kv_quant_append: wpos needs S == 1");
+  } else {
+    TORCH_CHECK(start >= 0 && start + S <= c.max_s, "kv_quant_append: rows ",
+                start, " .. ", start + S, " of a cache of ", c.max_s);
+  }
+  op.aligned16("k, v", {k.data_ptr(), v.data_ptr()});
+  if (B == 0 || S == 0) return;
+  launch_kv_quant_append(k.data_ptr(), v.data_ptr(), k8.data_ptr(),
+                         v8.data_ptr(), ks.data_ptr<float>(),
+                         vs.data_ptr<float>(), wp, B, S, c.Hkv, c.D, c.Bc,
+                         c.max_s, wp ? 0 : i32(start), op.stream);
+}
+
+// Decode over the int8 cache, every query head of a GQA group in one
+// block (kvq.hip). Live rows: len_dev (int32 [1] or [B], read by the
+// kernel only), else length, else the capacity.
+std::vector<Tensor> attn_decode_q8(Tensor q, Tensor k8, Tensor v8, Tensor ks,
+                                   Tensor vs, double scale,
+                                   OptTensor len_dev,
+                                   c10::optional<int64_t> length) {
+  const Op op("attn_decode_q8", q, BF16, "q");
+  TORCH_CHECK(q.dim() == 4 && q.size(1) == 1,
+              "attn_decode_q8: q must be [B,1,Hq,D]");
+  const KvqShape c = check_kvq(op, k8, v8, ks, vs);
+  const int B = i32(q.size(0)), Hq = i32(q.size(2));
+  TORCH_CHECK(q.size(3) == c.D, "attn_decode_q8: q has D = ", q.size(3),
+              ", the cache ", c.D);
+  TORCH_CHECK(B <= c.Bc, "attn_decode_q8: B = ", B, " rows for a cache of ",
+              c.Bc);
+  TORCH_CHECK(Hq >= 1 && Hq % c.Hkv == 0 && Hq / c.Hkv <= 16,
+              "attn_decode_q8: Hq % Hkv and a GQA group of at most 16, got ",
+              "Hq = ", Hq, ", Hkv = ", c.Hkv);
+  op.aligned16("q", {q.data_ptr()});
+  const int* ld = op.opt<int>(len_dev, I32, "len_dev");
+  TORCH_CHECK(!ld || len_dev->numel() == 1 || len_dev->numel() == B,
+              "attn_decode_q8: len_dev must be [1] or [B]");
+  TORCH_CHECK(!(ld && length.has_value()),
+              "attn_decode_q8: give len_dev or length, not both");
+  const long len = length.has_value() ? *length : c.max_s;
+  TORCH_CHECK(len >= 1 && len <= c.max_s, "attn_decode_q8: length ", len,
+              " of a cache of ", c.max_s);
+  const int len_stride = ld && len_dev->numel() > 1;
+  auto o = torch::empty_like(q);
+  auto lse = torch::empty({B, Hq, 1}, q.options().dtype(F32));
+  if (B == 0) return {o, lse};
+  auto part = torch::empty(
+      {(long)B * Hq, attn_decode_q8_nsplit(c.max_s, c.Hkv, c.D), c.D + 2},
+      lse.options());
+  launch_attn_decode_q8(q.data_ptr(), k8.data_ptr(), v8.data_ptr(),
+                        ks.data_ptr<float>(), vs.data_ptr<float>(), ld,
+                        i32(len), part.data_ptr<float>(), o.data_ptr(),
+                        lse.data_ptr<float>(), B, Hq, c.Hkv, c.max_s, c.D,
+                        (float)scale, len_stride, op.stream);
+  return {o, lse};
+}
+
 // All BSHD, read in place: nothing is transposed on the host side.
 std::vector<Tensor> attn_bwd(Tensor q, Tensor k, Tensor v, Tensor o,
                              Tensor dO, Tensor lse, bool causal,
@@ -923,4 +1018,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemm_nt_add_versions", &gemm_nt_add_versions_py);
   m.def("attn_decode", &attn_decode, py::arg("q"), py::arg("k"),
         py::arg("v"), py::arg("scale"), py::arg("len_dev") = py::none());
+  m.def("kv_quant_append", &kv_quant_append, py::arg("k"), py::arg("v"),
+        py::arg("k8"), py::arg("v8"), py::arg("ks"), py::arg("vs"),
+        py::arg("start") = 0, py::arg("wpos") = py::none());
+  m.def("attn_decode_q8", &attn_decode_q8, py::arg("q"), py::arg("k8"),
+        py::arg("v8"), py::arg("ks"), py::arg("vs"), py::arg("scale"),
+        py::arg("len_dev") = py::none(), py::arg("length") = py::none());
+  m.def("attn_decode_q8_nsplit", &attn_decode_q8_nsplit, py::arg("max_s"),
+        py::arg("hkv"), py::arg("d"));
 }

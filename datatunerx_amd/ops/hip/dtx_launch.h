@@ -149,6 +149,41 @@ void launch_attn_decode(const void* q, const void* k, const void* v,
                         float* lse, int B, int Hq, int Hkv, int Skv,
                         int D, float scale, int len_stride,
                         hipStream_t st);
+// The second half of launch_attn_decode alone: part [BH, NS, D+2] f32 ->
+// o [BH, D] bf16, lse [BH] f32. D is 64 or 128, NS >= 1.
+void launch_attn_decode_combine(const float* part, void* o, float* lse,
+                                int BH, int NS, int D, hipStream_t st);
+
+// -------------------------------------------------------------------- kvq.hip
+// int8 KV cache: k8, v8 [Bc, max_s, Hkv, D] int8, ks, vs [Bc, Hkv, max_s]
+// f32 (one scale per token and kv head). D is 64 or 128, anything else
+// launches nothing.
+// k, v [B,S,Hkv,D] bf16, quantized row by row into the cache; k, v, k8, v8
+// 16-byte aligned. Without wpos row (b, s) goes to slot (b, start + s):
+// B <= Bc, 0 <= start, start + S <= max_s. With wpos (int64 [B], S == 1)
+// row b goes to the flat slot wpos[b] of [Bc * max_s]; a value outside
+// that range is skipped in the kernel.
+void launch_kv_quant_append(const void* k, const void* v, void* k8,
+                            void* v8, float* ks, float* vs,
+                            const long long* wpos, long B, int S, int Hkv,
+                            int D, long Bc, int max_s, int start,
+                            hipStream_t st);
+// Split plan of the decode kernel: rows per chunk (a multiple of 128) and
+// chunks = planes of its part workspace. A function of the capacity and
+// the head shape alone, never of B or of the live lengths.
+int attn_decode_q8_chunk(int max_s, int Hkv, int D);
+int attn_decode_q8_nsplit(int max_s, int Hkv, int D);
+// q, o [B,1,Hq,D] bf16, q, k8, v8 16-byte aligned; B <= Bc; lse [B,Hq] f32;
+// part [B*Hq, attn_decode_q8_nsplit(max_s, Hkv, D), D+2] f32.
+// Hq % Hkv == 0 and 1 <= Hq / Hkv <= 16. Live rows of batch row b: len_dev
+// (one int32, or B of them when len_stride) read on the device, else
+// `length`; either is clamped to max_s in the kernel, <= 0 gives o = 0.
+void launch_attn_decode_q8(const void* q, const void* k8, const void* v8,
+                           const float* ks, const float* vs,
+                           const int* len_dev, int length, float* part,
+                           void* o, float* lse, int B, int Hq, int Hkv,
+                           int max_s, int D, float scale, int len_stride,
+                           hipStream_t st);
 // Shapes as launch_attn_fwd; dO, dq like q; dk, dv like k; lse, delta
 // [B,Hq,S] f32. dq runs first and writes delta, dkdv reads it. D is 64 or
 // 128, anything else launches nothing. doc_start / doc_end [B,S] int32,

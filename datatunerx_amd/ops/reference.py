@@ -315,6 +315,53 @@ def lora_expand_add(y: torch.Tensor, t: torch.Tensor, w: torch.Tensor,
     return y
 
 
+def kv_quant_append(k, v, k8, v8, ks, vs, start: int = 0, wpos=None):
+    """fp32 twin of kvq.hip's append: models/quant.py::quantize_int8 on
+    every D-element row of k, v [B,S,Hkv,D] (with q one step nearer where
+    the fp32 division put it past scale / 2 from x; the residual is exact
+    in fp64 here and one fp32 fma in the kernel, so on an element whose
+    residual is scale / 2 to within an fp32 rounding the two may pick
+    neighbouring q, both within the bound; no test compares their bits),
+    written into k8, v8
+    [Bc,max_s,Hkv,D] int8 and ks, vs [Bc,Hkv,max_s] f32. Row (b, s) goes
+    to slot (b, start + s), or with wpos (int64 [B], S == 1) to the flat
+    slot wpos[b] of [Bc * max_s]; a slot outside the cache is skipped."""
+    B, S, Hkv, D = k.shape
+    max_s = k8.shape[1]
+    if wpos is None:
+        slots = (torch.arange(B).view(B, 1) * max_s + start
+                 + torch.arange(S).view(1, S)).reshape(-1)
+    else:
+        slots = wpos.reshape(-1).cpu()
+    ok = (slots >= 0) & (slots < k8.shape[0] * max_s)
+    slots = slots[ok]
+    for x, x8, xs in ((k, k8, ks), (v, v8, vs)):
+        xf = x.float().reshape(B * S, Hkv, D)[ok]
+        scale = xf.abs().amax(dim=-1).clamp(min=1e-8) / 127.0
+        q = torch.round(xf / scale[..., None])
+        # the fp32 quotient of a value just under n + 1/2 can round up onto
+        # the tie: step back where q landed more than scale / 2 from x
+        res = xf.double() - q.double() * scale.double()[..., None]
+        half = scale.double()[..., None] / 2
+        q = q + (res > half).float() - (res < -half).float()
+        q = torch.clamp(q, -127, 127)
+        x8.view(-1, Hkv, D)[slots] = q.to(torch.int8)
+        xs[slots // max_s, :, slots % max_s] = scale
+
+
+def attn_decode_q8(q, k8, v8, ks, vs, scale, lens):
+    """fp32 twin of kvq.hip's decode: dequantize, then attn_fwd over the
+    first lens[b] rows of batch row b. q [B,1,Hq,D] -> (o, lse)."""
+    outs, lses = [], []
+    for b, n in enumerate(lens):
+        kf = k8[b:b + 1, :n].float() * ks[b, :, :n].t()[None, :, :, None]
+        vf = v8[b:b + 1, :n].float() * vs[b, :, :n].t()[None, :, :, None]
+        o, lse = attn_fwd(q[b:b + 1].float(), kf, vf, False, scale)
+        outs.append(o.to(q.dtype))
+        lses.append(lse)
+    return torch.cat(outs, 0), torch.cat(lses, 0)
+
+
 def mlora_add(y: torch.Tensor, x: torch.Tensor, A: torch.Tensor,
               Bt: torch.Tensor, scale: torch.Tensor, idx: torch.Tensor):
     """Per-row gathered LoRA update, in place on y [M,N]:

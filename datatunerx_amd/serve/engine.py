@@ -85,6 +85,68 @@ class KVCache:
                 self.v[:, :self.cur].contiguous(), None)
 
 
+class Int8KVCache:
+    """KVCache's int8 twin: k8, v8 int8 [B, max_s, Hkv, D] with one fp32
+    scale per (token, kv head) in ks, vs [B, Hkv, max_s] (per-row absmax,
+    models/quant.py::quantize_int8), written by ops.kv_quant_append and
+    read by ops.attn_decode_q8, which serves all query heads of a GQA
+    group from one pass over the cache.
+
+    update() keeps KVCache's contract in both modes, except for what it
+    hands to attention: a prefill (S > 1 onto the empty cache) returns
+    the fresh k, v it was given, and a decode step (S == 1) returns
+    (ops.KV8, None, len_dev), the handle LlamaAttention passes to
+    ops.attn_decode_q8. An S > 1 update onto a non-empty cache would
+    need attention over a quantized prefix and raises."""
+
+    def __init__(self, B, Hkv, max_s, D, device, dtype,
+                 wpos=None, len32=None):
+        self.k8 = torch.zeros(B, max_s, Hkv, D, device=device,
+                              dtype=torch.int8)
+        self.v8 = torch.zeros_like(self.k8)
+        self.ks = torch.zeros(B, Hkv, max_s, device=device,
+                              dtype=torch.float32)
+        self.vs = torch.zeros_like(self.ks)
+        self.cur = 0
+        self.wpos, self.len32 = wpos, len32
+
+    def row_view(self, i):
+        """Host-mode B = 1 cache over row i's storage."""
+        row = copy.copy(self)
+        row.k8, row.v8 = self.k8[i:i + 1], self.v8[i:i + 1]
+        row.ks, row.vs = self.ks[i:i + 1], self.vs[i:i + 1]
+        row.cur, row.wpos, row.len32 = 0, None, None
+        return row
+
+    def update(self, k, v):
+        from .. import ops
+        S = k.shape[1]
+        k, v = k.contiguous(), v.contiguous()
+        cache = (self.k8, self.v8, self.ks, self.vs)
+        if self.wpos is not None and S == 1:
+            ops.kv_quant_append(k, v, *cache, wpos=self.wpos)
+            return ops.KV8(*cache), None, self.len32
+        if S > 1 and self.cur > 0:
+            raise ValueError(
+                "int8 KV cache: a multi-token update onto a non-empty "
+                "cache (chunked prefill) is not supported")
+        ops.kv_quant_append(k, v, *cache, start=self.cur)
+        self.cur += S
+        if S == 1:
+            return ops.KV8(*cache, length=self.cur), None, None
+        return k, v, None                # prefill attends what came in
+
+
+KV_CACHES = {"bf16": KVCache, "int8": Int8KVCache}
+
+
+def _kv_cache_class(kind: str):
+    if kind not in KV_CACHES:
+        raise ValueError(f"unknown kv_cache {kind!r} "
+                         f"(expected one of {sorted(KV_CACHES)})")
+    return KV_CACHES[kind]
+
+
 class _DecodeState:
     """Counters and layer caches of one ragged decode batch. Row b's
     next token is written at index pos[b] (pos32 feeds rope, wpos ==
@@ -99,7 +161,8 @@ class _DecodeState:
     sampled, its RNG counter), so ops.sample draws every row of a step
     with that row's own setting; all-zero (the start) is greedy."""
 
-    def __init__(self, B, Hkv, max_s, D, layers, device, dtype):
+    def __init__(self, B, Hkv, max_s, D, layers, device, dtype,
+                 kv_cache="bf16"):
         self.B, self.max_s = B, max_s
         self._row0 = torch.arange(B, device=device) * max_s
         self.wpos = self._row0.clone()
@@ -111,8 +174,9 @@ class _DecodeState:
         self.top_k = torch.zeros(B, dtype=torch.int32, device=device)
         self.seed = torch.zeros(B, dtype=torch.int64, device=device)
         self.offset = torch.zeros(B, dtype=torch.int32, device=device)
-        self.caches = [KVCache(B, Hkv, max_s, D, device, dtype,
-                               wpos=self.wpos, len32=self.len32)
+        cache = _kv_cache_class(kv_cache)
+        self.caches = [cache(B, Hkv, max_s, D, device, dtype,
+                             wpos=self.wpos, len32=self.len32)
                        for _ in range(layers)]
 
     def set_state(self, lens):
@@ -165,10 +229,11 @@ class _GraphedDecoder(_DecodeState):
     buffers (a row at temperature 0 gets the same argmax, bit for bit),
     so one graph serves every mix of greedy and sampled rows."""
 
-    def __init__(self, model, cfg, device, B, max_s, sample=False):
+    def __init__(self, model, cfg, device, B, max_s, sample=False,
+                 kv_cache="bf16"):
         super().__init__(B, cfg.num_key_value_heads, max_s, cfg.head_dim,
                          cfg.num_hidden_layers, device,
-                         next(model.parameters()).dtype)
+                         next(model.parameters()).dtype, kv_cache)
         self.input = torch.ones(B, 1, dtype=torch.long, device=device)
         # -1 = base model / dummy row
         self.adapter_idx, akw = _graph_adapter_buffer(model, B, device)
@@ -359,12 +424,18 @@ class InferenceEngine:
 
     def __init__(self, model, tokenizer=None, template: str = "llama2",
                  device=None, graph_decode: bool = True,
-                 own_stream: bool = False):
+                 own_stream: bool = False, kv_cache: str = "bf16"):
+        """kv_cache: "bf16", or "int8" for the quantized KV cache (llama
+        models inside ops.kv_int8_supported, one GPU or the CPU)."""
         self.model = model
         self.tok = tokenizer or ByteTokenizer()
         self.template = template
         self.device = device or next(model.parameters()).device
         self.is_llama = isinstance(model, LlamaForCausalLM)
+        _kv_cache_class(kv_cache)
+        self.kv_cache = kv_cache
+        if kv_cache == "int8":
+            self._check_kv_int8()
         import torch.distributed as dist
         self._graphed = None
         self._bgraphed = None
@@ -406,6 +477,20 @@ class InferenceEngine:
                     self._stop_ids.add(int(ids[0]))
         except (KeyError, TypeError):
             pass
+
+    def _check_kv_int8(self):
+        """The int8 KV cache's contract, checked before any allocation."""
+        from .. import ops
+        if not self.is_llama:
+            raise ValueError("kv_cache='int8' supports llama models only")
+        cfg = self.model.cfg
+        if not ops.kv_int8_supported(cfg.num_attention_heads,
+                                     cfg.num_key_value_heads, cfg.head_dim):
+            raise ValueError(
+                f"kv_cache='int8' needs head_dim 64 or 128 and at most 16 "
+                f"query heads per kv head, got {cfg.num_attention_heads} "
+                f"heads, {cfg.num_key_value_heads} kv heads, head_dim "
+                f"{cfg.head_dim}")
 
     # ---------------------------------------------------- adapters
     def _adapter_index(self, adapter: Optional[str]) -> int:
@@ -453,7 +538,8 @@ class InferenceEngine:
             with InferenceEngine._capture_lock, self._stream_ctx():
                 return _GraphedDecoder(self.model, self.model.cfg,
                                        self.device, B, max_s,
-                                       sample=self.device_sampling)
+                                       sample=self.device_sampling,
+                                       kv_cache=self.kv_cache)
         except Exception:
             return None
 
@@ -666,9 +752,10 @@ class InferenceEngine:
             cfg = self.model.cfg
             max_s = min(cfg.max_position_embeddings,
                         len(prompt_ids) + max_new_tokens + 8)
-            caches = [KVCache(1, cfg.num_key_value_heads, max_s,
-                              cfg.head_dim, self.device,
-                              next(self.model.parameters()).dtype)
+            cache = _kv_cache_class(self.kv_cache)
+            caches = [cache(1, cfg.num_key_value_heads, max_s,
+                            cfg.head_dim, self.device,
+                            next(self.model.parameters()).dtype)
                       for _ in range(cfg.num_hidden_layers)]
             pos = 0
             cur = ids
@@ -797,7 +884,8 @@ class InferenceEngine:
         return _DecodeState(n, cfg.num_key_value_heads, max_s,
                             cfg.head_dim, cfg.num_hidden_layers,
                             self.device,
-                            next(self.model.parameters()).dtype)
+                            next(self.model.parameters()).dtype,
+                            self.kv_cache)
 
     def _batch_prefill(self, st, prompts, aidx, samp):
         """Prefill every row into st's caches and hand the row lengths

@@ -500,6 +500,10 @@ def parse_args(argv=None):
                     help="serve the base weights weight-only quantized "
                          "(adapters stay bf16, unmerged); single-GPU "
                          "llama models only")
+    ap.add_argument("--kv-cache", choices=("bf16", "int8"), default="bf16",
+                    help="KV cache format; int8 halves the cache and its "
+                         "decode traffic (single-GPU llama models inside "
+                         "ops.kv_int8_supported)")
     args = ap.parse_args(argv)
     args.adapter, args.adapters = _split_adapters(ap, args.adapter)
     return args
@@ -578,6 +582,31 @@ def _check_quantization(args, world: int):
                 f"--quantization supports llama models, not {args.model!r}")
 
 
+def _check_kv_cache(args, world: int):
+    """--kv-cache int8 is refused at start-up where it cannot be honoured
+    rather than silently serving the bf16 cache."""
+    if args.kv_cache != "int8":
+        return
+    if world > 1:
+        raise SystemExit(
+            "--kv-cache int8 is not supported with tensor-parallel serving "
+            f"(WORLD_SIZE={world}); serve it on one GPU")
+    from .engine import builtin_config
+    from ..models.hf_io import is_hf_model_dir
+    from ..ops import kv_int8_supported
+    if not is_hf_model_dir(args.model):
+        try:
+            family, cfg = builtin_config(args.model)
+        except ValueError as e:
+            raise SystemExit(str(e))
+        if family != "llama" or not kv_int8_supported(
+                cfg.num_attention_heads, cfg.num_key_value_heads,
+                cfg.head_dim):
+            raise SystemExit(
+                "--kv-cache int8 supports llama models with head_dim 64 or "
+                f"128 and a GQA group of at most 16, not {args.model!r}")
+
+
 def main(argv=None):
     import os
 
@@ -585,6 +614,7 @@ def main(argv=None):
     args = parse_args(argv)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     _check_quantization(args, world)
+    _check_kv_cache(args, world)
     _check_adapters(args, world)
     if world > 1:
         # tensor-parallel service (launched under torchrun, 1 rank/GPU):
@@ -654,14 +684,16 @@ def main(argv=None):
     n_slots = max(1, int(os.environ.get("DTX_SERVE_CONCURRENCY", "2")))
     pool = EnginePool([
         InferenceEngine(model, tokenizer=tok, template=args.template,
-                        device=device, own_stream=(n_slots > 1))
+                        device=device, own_stream=(n_slots > 1),
+                        kv_cache=args.kv_cache)
         for _ in range(n_slots)])
     batcher = None
     if os.environ.get("DTX_SERVE_BATCH", "1") != "0" and \
             isinstance(model, LlamaForCausalLM):
         batcher = BatchingFront(
             InferenceEngine(model, tokenizer=tok, template=args.template,
-                            device=device, own_stream=True),
+                            device=device, own_stream=True,
+                            kv_cache=args.kv_cache),
             max_batch=int(os.environ.get("DTX_SERVE_MAX_BATCH", "8")))
     httpd = ThreadingHTTPServer((args.host, args.port),
                                 build_handler(

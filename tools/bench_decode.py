@@ -57,9 +57,15 @@ def _attach_random_adapters(model, n, dev):
                                      [8] * n, 8, ("q_proj", "v_proj"))
 
 
-def build(dev, quantization, graph, adapters=0):
+def build(dev, quantization, graph, adapters=0, kv_cache="bf16",
+          model=None):
     """adapters: 0 none, -1 one adapter the single-adapter way (LoRA
-    modules, unmerged), N > 0 multi-adapter mode with N stacked."""
+    modules, unmerged), N > 0 multi-adapter mode with N stacked.
+    model: an engine's model to share (the KV-cache arms of one weight
+    format run over the same weights)."""
+    if model is not None:
+        return InferenceEngine(model, template="vanilla", device=dev,
+                               graph_decode=graph, kv_cache=kv_cache)
     torch.cuda.reset_peak_memory_stats()
     model = LlamaForCausalLM(LlamaConfig.llama2_7b(), lora=adapters < 0,
                              dtype=torch.bfloat16)
@@ -81,7 +87,7 @@ def build(dev, quantization, graph, adapters=0):
         torch.cuda.empty_cache()
     model.eval()
     return InferenceEngine(model, template="vanilla", device=dev,
-                           graph_decode=graph)
+                           graph_decode=graph, kv_cache=kv_cache)
 
 
 def sampling_kwargs(args, batch):
@@ -98,12 +104,12 @@ def sampling_kwargs(args, batch):
             "top_k": args.top_k, "seed": list(range(batch))}
 
 
-def run(eng, tokens, batch, skw=None):
+def run(eng, tokens, batch, skw=None, prompt_len=96):
     """One timed generation; returns decoded tokens per second (all
     rows). Random weights never emit a stop token reliably, so count
     what was actually produced. skw: sampling_kwargs()."""
     skw = skw or {}
-    prompt = list(range(5, 5 + 96))
+    prompt = [5 + i % 1000 for i in range(prompt_len)]
     reg = getattr(eng.model, "adapters", None)
     names = ([reg.names[i % len(reg)] for i in range(batch)]
              if reg is not None else None)
@@ -143,6 +149,11 @@ def main():
     ap.add_argument("--mixed", action="store_true",
                     help="rows alternate greedy and sampled (needs "
                          "--temperature and --batch > 1)")
+    ap.add_argument("--kv-cache", default="bf16",
+                    choices=("bf16", "int8", "both"),
+                    help="KV cache format; both: the two formats over the "
+                         "same weights, interleaved")
+    ap.add_argument("--prompt-len", type=int, default=96)
     args = ap.parse_args()
     if args.mixed and not (args.temperature > 0 and args.batch > 1):
         ap.error("--mixed needs --temperature > 0 and --batch > 1")
@@ -151,8 +162,10 @@ def main():
     if args.compare_adapters:
         compare_adapters(args, dev)
         return
-    arms = [None, "int8", "int4"] if args.quantization == "all" \
+    quants = [None, "int8", "int4"] if args.quantization == "all" \
         else [args.quantization]
+    kvs = ["bf16", "int8"] if args.kv_cache == "both" else [args.kv_cache]
+    arms = [(q, kv) for q in quants for kv in kvs]
     adapters = -1 if args.single_adapter else args.adapters
     if adapters:
         print(f"adapters: {'single' if adapters < 0 else adapters}",
@@ -160,20 +173,25 @@ def main():
     engines, mem = {}, {}
     for q in arms:
         # memory of this arm alone: relative to what earlier arms hold
+        # (a second KV arm shares the first one's weights)
         base = torch.cuda.memory_allocated()
-        engines[q] = build(dev, q, not args.no_graph, adapters)
-        run(engines[q], 8, args.batch, skw)    # warmup (captures the graph)
+        shared = engines.get((q[0], kvs[0]))
+        engines[q] = build(dev, q[0], not args.no_graph, adapters, q[1],
+                           shared.model if shared else None)
+        run(engines[q], 8, args.batch, skw, args.prompt_len)  # + capture
         mem[q] = (torch.cuda.memory_allocated() - base,
                   torch.cuda.max_memory_allocated() - base)
     rates = {q: [] for q in arms}
     for _ in range(args.reps):
         for q in arms:                     # arms alternate per repetition
-            rates[q].append(run(engines[q], args.tokens, args.batch, skw))
+            rates[q].append(run(engines[q], args.tokens, args.batch, skw,
+                                args.prompt_len))
     for q in arms:
         tps = statistics.median(r for r, _ in rates[q])
         n = rates[q][0][1]
         mode = ("mixed " if args.mixed else "sampled ") if skw else ""
-        print(f"{q or 'bf16'} graph={not args.no_graph} "
+        print(f"{q[0] or 'bf16'} kv={q[1]} prompt={args.prompt_len} "
+              f"graph={not args.no_graph} "
               f"{mode}batch={args.batch}: {n} tokens, {tps:.1f} tok/s "
               f"(min {min(r for r, _ in rates[q]):.1f}, "
               f"max {max(r for r, _ in rates[q]):.1f}); allocated "
