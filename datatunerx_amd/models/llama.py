@@ -16,7 +16,8 @@ from dataclasses import dataclass
 import torch
 import torch.nn as nn
 
-from ..ops import KV8, attn_decode_q8, doc_end_from_start, rope_tables
+from ..ops import (KV8, attn_decode_q8, doc_end_from_start, rope_tables,
+                   skinny_decode_rows, skinny_swiglu)
 from ..ops.autograd import (PairedFrozenGemm, QKVProj, attention,
                             cross_entropy, rmsnorm, rmsnorm_tap,
                             rope, swiglu)
@@ -232,6 +233,14 @@ class LlamaMLP(nn.Module):
 
     def forward(self, x, residual=None, adapters=None):
         if type(self.gate_proj) is FrozenLinear and \
+                type(self.up_proj) is FrozenLinear and \
+                not self.gate_proj.weight.requires_grad and \
+                not self.up_proj.weight.requires_grad and \
+                skinny_decode_rows(x):
+            # decode (1-16 rows, no grad): both GEMMs and the SwiGLU in
+            # one kernel, g and u never reach HBM
+            h = skinny_swiglu(x, self.gate_proj.weight, self.up_proj.weight)
+        elif type(self.gate_proj) is FrozenLinear and \
                 type(self.up_proj) is FrozenLinear and \
                 not self.gate_proj.weight.requires_grad:
             # one node for the gate/up pair: backward accumulates both

@@ -19,7 +19,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from ..ops import gemm_nt_supported
+from ..ops import gemm_nt_supported, skinny_decode_rows, skinny_linear
 from ..ops.autograd import FrozenGemm
 from ..ops.autograd import LoRALinear as _FusedLoRAFn
 
@@ -136,6 +136,10 @@ class FrozenLinear(nn.Module):
             from ..ops import gemv
             y = gemv(x, self.weight)         # decode: streaming GEMV
             return y if residual is None else y + residual
+        if not self.weight.requires_grad and skinny_decode_rows(x, 2):
+            # batched decode (2-16 rows, no grad): the weight-streaming
+            # kernel, the residual in its epilogue
+            return skinny_linear(x, self.weight, residual)
         if not self.weight.requires_grad:
             # one node: residual add in the GEMM epilogue without a copy
             # of the residual, dgrad against the cached W^T

@@ -320,6 +320,97 @@ def gemm_nt_add(a, b, c):
     return torch.addmm(c, a, b.t())
 
 
+# --------------------------------------------- skinny bf16 decode GEMMs
+SKINNY_MAX_ROWS = 16
+
+
+def skinny_supported(M: int, N: int, K: int) -> bool:
+    """Shapes the bf16 weight-streaming kernels take (skinny.hip): 1 to 16
+    rows, K in whole 16-byte pieces. The predicate is the extension's own
+    (the one its bindings check)."""
+    ext = _load_ext()
+    if ext is None:
+        raise RuntimeError("skinny_supported needs the HIP extension "
+                           f"(_dtx_hip): {_EXT_ERR}")
+    return bool(ext.skinny_supported(M, N, K))
+
+
+def _skinny_ok(x, *ws) -> bool:
+    """Does the kernel take this call? bf16, dense, 16-byte aligned,
+    skinny_supported, and DTX_SKINNY_GEMM != 0."""
+    if os.environ.get("DTX_SKINNY_GEMM", "1") == "0":
+        return False
+    K = x.shape[-1]
+    if not (x.dtype == torch.bfloat16 and K > 0 and x.is_contiguous()
+            and x.data_ptr() % 16 == 0):
+        return False
+    M = x.numel() // K
+    return all(w.dtype == torch.bfloat16 and w.dim() == 2
+               and w.shape[1] == K and w.is_contiguous()
+               and w.data_ptr() % 16 == 0 and w.device == x.device
+               and _EXT.skinny_supported(M, max(w.shape[0], 1), K)
+               for w in ws)
+
+
+def skinny_decode_rows(x, min_rows: int = 1, no_grad=None) -> bool:
+    """Call-site test: a no-grad bf16 GPU activation of min_rows..16 rows,
+    the calls the skinny kernels are for (the op still checks the rest).
+    no_grad: for autograd nodes, whose forward always runs with grad mode
+    off: whether no input of the node needs a gradient."""
+    if no_grad is None:
+        no_grad = not torch.is_grad_enabled()
+    if not no_grad or not x.is_cuda or x.dtype != torch.bfloat16 or \
+            x.shape[-1] == 0:
+        return False
+    return min_rows <= x.numel() // x.shape[-1] <= SKINNY_MAX_ROWS
+
+
+def skinny_linear(x, w, residual=None):
+    """y[...,N] = x[...,K] @ w[N,K]^T (+ residual [...,N]) for decode-sized
+    x. GPU: the weight-streaming MFMA kernel where _skinny_ok, else what
+    ran before it (F.linear; gemm_nt_add / addmm with a residual)."""
+    if _gpu(x):
+        N = w.shape[0]
+        if _skinny_ok(x, w) and (residual is None or (
+                residual.dtype == torch.bfloat16
+                and residual.numel() == x.numel() // x.shape[-1] * N)):
+            r = None if residual is None else residual.contiguous()
+            return _EXT.skinny_gemm(x, w, r)
+        if residual is None:
+            return torch.nn.functional.linear(x, w)
+        x2 = x.reshape(-1, x.shape[-1])
+        r2 = residual.reshape(-1, N).contiguous()
+        if x2.dtype == torch.bfloat16 and x2.shape[0] > 1:
+            y = _EXT.gemm_nt_add(x2.contiguous(), w.contiguous(), r2)
+        else:
+            y = torch.addmm(r2, x2, w.t())
+        return y.reshape(*x.shape[:-1], N)
+    return ref.skinny_linear(x, w, residual)
+
+
+def skinny_linear_multi(x, ws):
+    """[x @ w^T for w in ws] for up to three weights that share x (q/k/v):
+    one grouped launch, each output bit-identical to skinny_linear(x, w)."""
+    ws = list(ws)
+    if _gpu(x):
+        if 1 <= len(ws) <= 3 and _skinny_ok(x, *ws):
+            return list(_EXT.skinny_gemm_multi(x, ws))
+        return [torch.nn.functional.linear(x, w) for w in ws]
+    return ref.skinny_linear_multi(x, ws)
+
+
+def skinny_swiglu(x, wg, wu):
+    """swiglu(x @ wg^T, x @ wu^T) with the two products rounded to bf16
+    as the two-GEMM path stores them; on the kernel path g and u never
+    reach HBM."""
+    if _gpu(x):
+        if wg.shape == wu.shape and _skinny_ok(x, wg, wu):
+            return _EXT.skinny_swiglu(x, wg, wu)
+        return swiglu_fwd(torch.nn.functional.linear(x, wg).contiguous(),
+                          torch.nn.functional.linear(x, wu).contiguous())
+    return ref.skinny_swiglu(x, wg, wu)
+
+
 # -------------------------------------------------------------- LoRA
 # Dropout enters the kernels one of two ways:
 #   - `mask`: a materialized bf16 mask tensor (same shape as x / y)

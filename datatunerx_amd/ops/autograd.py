@@ -13,6 +13,7 @@ import torch
 from . import (attn_bwd, attn_fwd, gemm_nt_add, lora_contract,
                lora_contract2, lora_expand_add2, lora_expand_add_t,
                lora_wgrad, rmsnorm_bwd, rmsnorm_fwd, rope_bwd, rope_fwd,
+               skinny_decode_rows, skinny_linear, skinny_linear_multi,
                softmax_xent_bwd, softmax_xent_fwd, swiglu_bwd, swiglu_fwd)
 
 
@@ -241,6 +242,9 @@ class LoRALinear(torch.autograd.Function):
         if x2.is_cuda and x2.shape[0] == 1 and keep >= 1.0:
             from . import gemv
             y = gemv(x2, w)                      # decode: streaming GEMV
+        elif keep >= 1.0 and skinny_decode_rows(
+                x2, 2, not any(ctx.needs_input_grad)):
+            y = skinny_linear(x2, w)             # batched decode: 2-16 rows
         else:
             y = _base_gemm(x2, w, custom)
         bt = b.t().contiguous()                  # [r,N]
@@ -292,6 +296,9 @@ class FrozenGemm(torch.autograd.Function):
         if custom:
             from . import gemm_nt
             y = gemm_nt(x2, w, r2)
+        elif r2 is not None and skinny_decode_rows(
+                x2, 2, not any(ctx.needs_input_grad)):
+            y = skinny_linear(x2, w, r2)         # batched decode: 2-16 rows
         elif r2 is None:
             y = torch.nn.functional.linear(x2, w)
         elif x2.is_cuda and not (x2.dtype == torch.bfloat16
@@ -442,9 +449,13 @@ class QKVProj(torch.autograd.Function):
                 seed_q, seed_v, keep, wqt=None, wkt=None, wvt=None):
         xs = x.shape
         x2 = x.reshape(-1, xs[-1])
-        yq = torch.nn.functional.linear(x2, wq)
-        yk = torch.nn.functional.linear(x2, wk)
-        yv = torch.nn.functional.linear(x2, wv)
+        if skinny_decode_rows(x2, 1, not any(ctx.needs_input_grad)):
+            # decode: the three base GEMMs in one grouped launch
+            yq, yk, yv = skinny_linear_multi(x2, [wq, wk, wv])
+        else:
+            yq = torch.nn.functional.linear(x2, wq)
+            yk = torch.nn.functional.linear(x2, wk)
+            yv = torch.nn.functional.linear(x2, wv)
         bqt = bq.t().contiguous()                # [r,Nq]
         bvt = bv.t().contiguous()                # [r,Nv]
         tq, tv = lora_contract2(x2, aq, av, seed_q, seed_v, keep)

@@ -702,6 +702,81 @@ Tensor qgemv_int4(Tensor x, Tensor packed, Tensor scale, long group) {
   return y;
 }
 
+// bf16 decode at 1..16 rows: y = x @ W^T streaming the checkpoint's [N,K]
+// weight (skinny.hip). The only allocations are the outputs:
+// hipGraph-capturable. Checks x [..., K] and one weight against
+// skinny_supported; returns N.
+int skinny_weight(const Op& op, const Tensor& x, const Tensor& w,
+                  const char* name) {
+  op.dense(w, BF16, name);
+  TORCH_CHECK(w.dim() == 2 && w.size(1) == x.size(-1), op.op, ": ", name,
+              " must be [N,", x.size(-1), "], got ", w.sizes());
+  const long M = op.rows(x, "x"), N = w.size(0), K = w.size(1);
+  TORCH_CHECK(skinny_supported(M, N ? N : 1, K), op.op,
+              ": outside the kernel contract (1 <= M <= 16, K % 8), got M=",
+              M, " N=", N, " K=", K);
+  op.aligned16(name, {w.data_ptr()});
+  return i32(N);
+}
+
+Tensor skinny_out(const Tensor& x, long N) {
+  auto sizes = x.sizes().vec();
+  sizes.back() = N;
+  return torch::empty(sizes, x.options());
+}
+
+std::vector<Tensor> skinny_gemm_multi(Tensor x, std::vector<Tensor> ws) {
+  const Op op("skinny_gemm_multi", x, BF16, "x");
+  TORCH_CHECK(ws.size() >= 1 && ws.size() <= 3,
+              "skinny_gemm_multi: 1 to 3 weights, got ", ws.size());
+  op.aligned16("x", {x.data_ptr()});
+  std::vector<Tensor> ys;
+  const void* wp[3];
+  void* yp[3];
+  int Ns[3], nw = 0;
+  for (const Tensor& w : ws) {
+    const int N = skinny_weight(op, x, w, "weight");
+    ys.push_back(skinny_out(x, N));
+    if (N == 0) continue;                  // empty output: not launched
+    wp[nw] = w.data_ptr();
+    yp[nw] = ys.back().data_ptr();
+    Ns[nw++] = N;
+  }
+  if (nw > 0)
+    launch_skinny_gemm(x.data_ptr(), wp, nullptr, yp, Ns, nw,
+                       i32(op.rows(x, "x")), i32(x.size(-1)), op.stream);
+  return ys;
+}
+
+Tensor skinny_gemm(Tensor x, Tensor w, OptTensor residual) {
+  const Op op("skinny_gemm", x, BF16, "x");
+  op.aligned16("x", {x.data_ptr()});
+  const int N = skinny_weight(op, x, w, "weight");
+  const long M = op.rows(x, "x");
+  const void* rp = op.opt(residual, BF16, "residual", M * N);
+  auto y = skinny_out(x, N);
+  if (N == 0) return y;
+  const void* wp = w.data_ptr();
+  void* yp = y.data_ptr();
+  launch_skinny_gemm(x.data_ptr(), &wp, rp, &yp, &N, 1, i32(M),
+                     i32(x.size(-1)), op.stream);
+  return y;
+}
+
+Tensor skinny_swiglu(Tensor x, Tensor wg, Tensor wu) {
+  const Op op("skinny_swiglu", x, BF16, "x");
+  op.aligned16("x", {x.data_ptr()});
+  const int N = skinny_weight(op, x, wg, "wg");
+  skinny_weight(op, x, wu, "wu");
+  op.shape(wu, wg.sizes(), "wu");
+  auto y = skinny_out(x, N);
+  if (N == 0) return y;
+  launch_skinny_swiglu(x.data_ptr(), wg.data_ptr(), wu.data_ptr(),
+                       y.data_ptr(), i32(op.rows(x, "x")), N,
+                       i32(x.size(-1)), op.stream);
+  return y;
+}
+
 // Multi-adapter decode: y[m] += scale[g] * (x[m] @ A[g]^T) @ Bt[g] with
 // g = idx[m] read ON THE DEVICE (mlora.hip); rows with an index outside
 // [0,G) are left untouched. Nothing here looks at idx's content and the
@@ -1004,6 +1079,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("scale"));
   m.def("qgemv_int4", &qgemv_int4, py::arg("x"), py::arg("packed"),
         py::arg("scale"), py::arg("group") = 64);
+  m.def("skinny_supported", &skinny_supported, py::arg("m"), py::arg("n"),
+        py::arg("k"));
+  m.def("skinny_gemm", &skinny_gemm, py::arg("x"), py::arg("w"),
+        py::arg("residual") = py::none());
+  m.def("skinny_gemm_multi", &skinny_gemm_multi, py::arg("x"),
+        py::arg("ws"));
+  m.def("skinny_swiglu", &skinny_swiglu, py::arg("x"), py::arg("wg"),
+        py::arg("wu"));
   m.def("mlora_add", &mlora_add, py::arg("y"), py::arg("x"), py::arg("A"),
         py::arg("Bt"), py::arg("scale"), py::arg("idx"));
   m.def("sample", &sample, py::arg("logits"), py::arg("temperature"),

@@ -59,6 +59,14 @@ __device__ __forceinline__ unsigned dtx_cvt_pk_bf16(float lo, float hi) {
   return r;
 }
 
+// silu(g) * u: the one SwiGLU formula (swiglu_fwd and the skinny GEMM's
+// gate/up epilogue). v_rcp_f32 (1 ulp) — the IEEE division chain is ~10
+// VALU ops.
+__device__ __forceinline__ float dtx_swiglu(float g, float u) {
+  float sig = __builtin_amdgcn_rcpf(1.f + __expf(-g));
+  return g * sig * u;
+}
+
 // Counter-based dropout RNG (splitmix64 on the element-group index):
 // the SAME (seed, linear-offset) pair yields the same mask bits in
 // every kernel that consumes it (contract / wgrad / expand), so the

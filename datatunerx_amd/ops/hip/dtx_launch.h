@@ -224,6 +224,24 @@ int gemm_nt_add_versions(int device, int* header, int* loaded,
 void launch_gemv_bf16(const void* x, const void* w, void* y, int N, int K,
                       hipStream_t st);
 
+// ----------------------------------------------------------------- skinny.hip
+// Shapes the bf16 weight-streaming kernels take and win at: 1 <= M <= 16,
+// N >= 1, K >= 8, K % 8 == 0, K <= 2^24, and M <= 2 where N >= 16384 (the
+// library ties or wins there). The one predicate of the family: the
+// bindings check it and Python routes by it.
+bool skinny_supported(long M, long N, long K);
+// y[i][M,N[i]] = x[M,K] @ w[i][N[i],K]^T for nw in 1..3 weights in one
+// grid, bf16; + residual [M,N[0]] (or nullptr) when nw == 1. x and every
+// w[i] 16-byte aligned, skinny_supported(M, N[i], K). The grid and an
+// output's summation order depend on (N[i], K) alone: each y[i] has the
+// bits of its single-weight launch, a row's bits do not depend on M.
+void launch_skinny_gemm(const void* x, const void* const* w,
+                        const void* residual, void* const* y, const int* N,
+                        int nw, int M, int K, hipStream_t st);
+// y[M,N] = swiglu(bf16(x @ wg^T), bf16(x @ wu^T)); wg, wu [N,K]. As above.
+void launch_skinny_swiglu(const void* x, const void* wg, const void* wu,
+                          void* y, int M, int N, int K, hipStream_t st);
+
 // ------------------------------------------------------ qgemv.hip, mlora.hip
 // y[M,N] = x[M,K] @ dequant(q)[N,K]^T. 1 <= M <= 16; x, q 16-byte aligned.
 // int8: q [N,K], scale [N], K % 16 == 0. int4: packed [N,K/2], scale

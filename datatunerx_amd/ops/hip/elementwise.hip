@@ -238,11 +238,7 @@ void swiglu_fwd_kernel(const unsigned short* __restrict__ gate,
     load_bf16x8(gate + idx * 8, g);
     load_bf16x8(up + idx * 8, u);
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      // v_rcp_f32 (1 ulp) — the IEEE division chain is ~10 VALU ops
-      float sig = __builtin_amdgcn_rcpf(1.f + __expf(-g[i]));
-      o[i] = g[i] * sig * u[i];
-    }
+    for (int i = 0; i < 8; ++i) o[i] = dtx_swiglu(g[i], u[i]);
     store_bf16x8(out + idx * 8, o);
   }
 }

@@ -534,3 +534,24 @@ def sample(logits: torch.Tensor, temperature: torch.Tensor,
     last = V - 1 - member.flip(1).to(torch.int8).argmax(1)
     tok = torch.where(hit.any(1), first, last)
     return torch.where(greedy.view(B), x.argmax(1), tok)
+
+
+# --------------------------------------------- skinny bf16 decode GEMMs
+def skinny_linear(x: torch.Tensor, w: torch.Tensor, residual=None):
+    """y[...,N] = x[...,K] @ w[N,K]^T (+ residual), fp32 accumulate, one
+    rounding to x's dtype."""
+    y = x.float() @ w.float().t()
+    if residual is not None:
+        y = y + residual.float().reshape(y.shape)
+    return y.to(x.dtype)
+
+
+def skinny_linear_multi(x: torch.Tensor, ws):
+    """One skinny_linear per weight (the GPU op shares a launch)."""
+    return [skinny_linear(x, w) for w in ws]
+
+
+def skinny_swiglu(x: torch.Tensor, wg: torch.Tensor, wu: torch.Tensor):
+    """swiglu of the two projections, each rounded to x's dtype first as
+    the two-GEMM path stores them."""
+    return swiglu_fwd(skinny_linear(x, wg), skinny_linear(x, wu))

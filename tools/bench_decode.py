@@ -154,6 +154,9 @@ def main():
                     help="KV cache format; both: the two formats over the "
                          "same weights, interleaved")
     ap.add_argument("--prompt-len", type=int, default=96)
+    ap.add_argument("--skinny-ab", action="store_true",
+                    help="bf16 with DTX_SKINNY_GEMM=0 and =1 over the same "
+                         "weights, interleaved")
     args = ap.parse_args()
     if args.mixed and not (args.temperature > 0 and args.batch > 1):
         ap.error("--mixed needs --temperature > 0 and --batch > 1")
@@ -161,6 +164,9 @@ def main():
     dev = torch.device("cuda")
     if args.compare_adapters:
         compare_adapters(args, dev)
+        return
+    if args.skinny_ab:
+        skinny_ab(args, dev, skw)
         return
     quants = [None, "int8", "int4"] if args.quantization == "all" \
         else [args.quantization]
@@ -198,6 +204,32 @@ def main():
               f"{mem[q][0] / 2**30:.2f} GiB steady, "
               f"{mem[q][1] / 2**30:.2f} GiB peak (build + warmup)",
               flush=True)
+
+
+def skinny_ab(args, dev, skw):
+    """bf16 decode with the skinny GEMMs off and on: two engines over one
+    model, each warmed (and its graph captured) under its own setting of
+    DTX_SKINNY_GEMM, then timed alternating per repetition."""
+    engines = {}
+    for knob in ("0", "1"):
+        os.environ["DTX_SKINNY_GEMM"] = knob
+        first = engines.get("0")
+        engines[knob] = build(dev, None, not args.no_graph,
+                              -1 if args.single_adapter else 0, args.kv_cache,
+                              first.model if first else None)
+        run(engines[knob], 8, args.batch, skw, args.prompt_len)
+    rates = {knob: [] for knob in engines}
+    for _ in range(args.reps):
+        for knob, eng in engines.items():
+            os.environ["DTX_SKINNY_GEMM"] = knob
+            rates[knob].append(run(eng, args.tokens, args.batch, skw,
+                                   args.prompt_len)[0])
+    base = statistics.median(rates["0"])
+    for knob in engines:
+        tps = statistics.median(rates[knob])
+        print(f"bf16 batch={args.batch} DTX_SKINNY_GEMM={knob}: {tps:.1f} "
+              f"tok/s (min {min(rates[knob]):.1f}, max "
+              f"{max(rates[knob]):.1f}), {tps / base:.3f}x off", flush=True)
 
 
 def compare_adapters(args, dev):
