@@ -177,10 +177,20 @@ def attn_fwd(q, k, v, causal: bool = True, scale: float | None = None,
             # serving decode: flash-decoding split-KV path (with S=1
             # every cached position is visible, causal or not).
             # len_dev: device-resident cache length (hipGraph decode).
+            # A GQA model's cache rows are shared by the query heads of
+            # their kv head (attn_decode_gqa.hip); MHA keeps its kernel.
+            if _gqa_decode_ok(q, k):
+                return _EXT.attn_decode_gqa(q, k, v, scale, len_dev)
             return _EXT.attn_decode(q, k, v, scale, len_dev)
         # V consumed row-major (PV B-frags via ds_read_b64_tr_b16):
         # no V pre-transpose
         return _EXT.attn_fwd(q, k, v.contiguous(), causal, scale)
+    return _attn_fwd_cpu(q, k, v, causal, scale, len_dev)
+
+
+def _attn_fwd_cpu(q, k, v, causal, scale, len_dev):
+    """The fp32 reference with the serving arguments: len_dev is one cache
+    length or one per batch row."""
     if len_dev is not None and len_dev.numel() > 1:
         # batched ragged decode on CPU: per-row cache lengths
         outs, lses = [], []
@@ -195,6 +205,53 @@ def attn_fwd(q, k, v, causal: bool = True, scale: float | None = None,
         k = k[:, :int(len_dev)]
         v = v[:, :int(len_dev)]
     return ref.attn_fwd(q, k, v, causal, scale)
+
+
+def gqa_decode_supported(Hq: int, Hkv: int, D: int) -> bool:
+    """Head shapes the GQA-shared bf16 decode kernel takes
+    (attn_decode_gqa.hip): head_dim 64 or 128 and 2 to 16 query heads per
+    kv head. The predicate is the extension's own (the one its binding
+    checks)."""
+    ext = _load_ext()
+    if ext is None:
+        raise RuntimeError("gqa_decode_supported needs the HIP extension "
+                           f"(_dtx_hip): {_EXT_ERR}")
+    return bool(ext.gqa_decode_supported(Hq, Hkv, D))
+
+
+def _gqa_decode_ok(q, k) -> bool:
+    """attn_fwd's S == 1 routing, DTX_GQA_DECODE read per call: 0 never,
+    1 wherever the kernel applies, unset where it was measured not to
+    lose (profiles/README.md, "GQA-shared bf16 decode"): groups above 4,
+    and groups up to 4 from a capacity of 8192 rows. At G = 4 and 2048
+    rows it lost 23-25 % on short live lengths at B >= 8."""
+    knob = os.environ.get("DTX_GQA_DECODE", "")
+    if knob == "0" or q.dim() != 4 or k.dim() != 4:
+        return False
+    Hq, Hkv = q.shape[2], k.shape[2]
+    if not _EXT.gqa_decode_supported(Hq, Hkv, q.shape[3]):
+        return False
+    return knob == "1" or Hq // Hkv > 4 or k.shape[1] >= 8192
+
+
+def attn_decode_gqa(q, k, v, scale: float | None = None, len_dev=None):
+    """Decode attention of q [B,1,Hq,D] over the bf16 KV cache k, v
+    [B,Skv,Hkv,D] -> (o [B,1,Hq,D], lse [B,Hq,1]), all query heads of a
+    GQA group sharing one pass over their kv head's rows. attn_decode's
+    contract (k, v may be the B == 1 prefix view of a larger cache;
+    len_dev int32 [1] or [B], read on the device and clamped to Skv);
+    needs gqa_decode_supported(Hq, Hkv, D). ops.attn_fwd routes here."""
+    if scale is None:
+        scale = 1.0 / (q.shape[-1] ** 0.5)
+    if _gpu(q):
+        return _EXT.attn_decode_gqa(q, k, v, scale, len_dev)
+    if q.dim() != 4 or q.shape[1] != 1:
+        raise ValueError("attn_decode_gqa: q must be [B,1,Hq,D]")
+    if len_dev is not None:
+        if len_dev.numel() not in (1, q.shape[0]):
+            raise ValueError("attn_decode_gqa: len_dev must be [1] or [B]")
+        len_dev = len_dev.clamp(max=k.shape[1])
+    return _attn_fwd_cpu(q, k, v, False, scale, len_dev)
 
 
 def attn_bwd(q, k, v, o, do, lse, causal: bool = True,

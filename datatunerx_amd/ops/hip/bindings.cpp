@@ -853,19 +853,26 @@ Tensor sample(Tensor logits, Tensor temperature, Tensor top_p, Tensor top_k,
 // prefix of a preallocated cache): the inner strides must be dense, the
 // batch stride only matters for B > 1. The values inside len_dev (<= Skv)
 // are the caller's contract.
-std::vector<Tensor> attn_decode(Tensor q, Tensor k, Tensor v, double scale,
-                                OptTensor len_dev) {
-  const Op op("attn_decode", q, BF16, "q");
-  TORCH_CHECK(q.dim() == 4 && q.size(1) == 1,
-              "attn_decode: q must be [B,1,Hq,D] (decode path wants S == 1)");
+// gqa: the kernel that shares a cache row among the query heads of its kv
+// head (attn_decode_gqa.hip): the same arguments and results, head shapes
+// within gqa_decode_supported, len_dev values clamped to Skv in the kernel.
+std::vector<Tensor> attn_decode_any(const char* name, bool gqa, Tensor q,
+                                    Tensor k, Tensor v, double scale,
+                                    OptTensor len_dev) {
+  const Op op(name, q, BF16, "q");
+  TORCH_CHECK(q.dim() == 4 && q.size(1) == 1, name,
+              ": q must be [B,1,Hq,D] (decode path wants S == 1)");
   const int B = i32(q.size(0)), Hq = i32(q.size(2)), D = i32(q.size(3));
-  TORCH_CHECK(D == 64 || D == 128, "attn_decode: D must be 64 or 128");
+  TORCH_CHECK(D == 64 || D == 128, name, ": D must be 64 or 128");
   TORCH_CHECK(op.dev(k, BF16, "k").dim() == 4 && k.size(0) == B &&
-              k.size(3) == D, "attn_decode: k must be [B,Skv,Hkv,D]");
+              k.size(3) == D, name, ": k must be [B,Skv,Hkv,D]");
   op.shape(op.dev(v, BF16, "v"), k.sizes(), "v");
   const int Skv = i32(k.size(1)), Hkv = i32(k.size(2));
-  TORCH_CHECK(Skv >= 1 && Hkv >= 1 && Hq >= 1 && Hq % Hkv == 0,
-              "attn_decode: Skv >= 1, Hq % Hkv (GQA group)");
+  TORCH_CHECK(Skv >= 1 && Hkv >= 1 && Hq >= 1 && Hq % Hkv == 0, name,
+              ": Skv >= 1, Hq % Hkv (GQA group)");
+  TORCH_CHECK(!gqa || gqa_decode_supported(Hq, Hkv, D), name,
+              ": a GQA group of 2 to 16 query heads per kv head, got Hq = ",
+              Hq, ", Hkv = ", Hkv);
   auto dense_kv = [&](const Tensor& t, const char* n) {
     TORCH_CHECK(t.stride(3) == 1 && t.stride(2) == D &&
                 t.stride(1) == (long)Hkv * D, n, " must be s/h/d-dense");
@@ -881,13 +888,24 @@ std::vector<Tensor> attn_decode(Tensor q, Tensor k, Tensor v, double scale,
   auto o = torch::empty_like(q);
   auto lse = torch::empty({B, Hq, 1}, q.options().dtype(F32));
   if (B == 0) return {o, lse};
-  auto part = torch::empty({(long)B * Hq, attn_decode_nsplit(Skv), D + 2},
-                           lse.options());
-  launch_attn_decode(q.data_ptr(), k.data_ptr(), v.data_ptr(), ld,
-                     part.data_ptr<float>(), o.data_ptr(),
-                     lse.data_ptr<float>(), B, Hq, Hkv, Skv, D,
-                     (float)scale, len_stride, op.stream);
+  const int ns = gqa ? attn_decode_gqa_nsplit(Skv, Hkv, D)
+                     : attn_decode_nsplit(Skv);
+  auto part = torch::empty({(long)B * Hq, ns, D + 2}, lse.options());
+  (gqa ? launch_attn_decode_gqa : launch_attn_decode)(
+      q.data_ptr(), k.data_ptr(), v.data_ptr(), ld, part.data_ptr<float>(),
+      o.data_ptr(), lse.data_ptr<float>(), B, Hq, Hkv, Skv, D, (float)scale,
+      len_stride, op.stream);
   return {o, lse};
+}
+
+std::vector<Tensor> attn_decode(Tensor q, Tensor k, Tensor v, double scale,
+                                OptTensor len_dev) {
+  return attn_decode_any("attn_decode", false, q, k, v, scale, len_dev);
+}
+
+std::vector<Tensor> attn_decode_gqa(Tensor q, Tensor k, Tensor v,
+                                    double scale, OptTensor len_dev) {
+  return attn_decode_any("attn_decode_gqa", true, q, k, v, scale, len_dev);
 }
 
 // ------------------------------------------------------ int8 KV cache
@@ -1101,6 +1119,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemm_nt_add_versions", &gemm_nt_add_versions_py);
   m.def("attn_decode", &attn_decode, py::arg("q"), py::arg("k"),
         py::arg("v"), py::arg("scale"), py::arg("len_dev") = py::none());
+  m.def("attn_decode_gqa", &attn_decode_gqa, py::arg("q"), py::arg("k"),
+        py::arg("v"), py::arg("scale"), py::arg("len_dev") = py::none());
+  m.def("gqa_decode_supported", &gqa_decode_supported, py::arg("hq"),
+        py::arg("hkv"), py::arg("d"));
+  m.def("attn_decode_gqa_chunk", &attn_decode_gqa_chunk, py::arg("skv"),
+        py::arg("hkv"), py::arg("d"));
+  m.def("attn_decode_gqa_nsplit", &attn_decode_gqa_nsplit, py::arg("skv"),
+        py::arg("hkv"), py::arg("d"));
   m.def("kv_quant_append", &kv_quant_append, py::arg("k"), py::arg("v"),
         py::arg("k8"), py::arg("v8"), py::arg("ks"), py::arg("vs"),
         py::arg("start") = 0, py::arg("wpos") = py::none());

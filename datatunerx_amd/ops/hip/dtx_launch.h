@@ -154,6 +154,29 @@ void launch_attn_decode(const void* q, const void* k, const void* v,
 void launch_attn_decode_combine(const float* part, void* o, float* lse,
                                 int BH, int NS, int D, hipStream_t st);
 
+// -------------------------------------------------------- attn_decode_gqa.hip
+// Head shapes the GQA-shared bf16 decode kernel takes: D in {64, 128},
+// Hq % Hkv == 0 and a group of 2 .. 16 query heads per kv head. The one
+// predicate: the binding checks it and Python routes by it.
+bool gqa_decode_supported(int Hq, int Hkv, int D);
+// Split plan: rows per chunk (a multiple of 128) and chunks (at most 32) =
+// planes of the part workspace. A function of the addressed capacity and
+// the head shape alone, never of B or of the live lengths.
+int attn_decode_gqa_chunk(int Skv, int Hkv, int D);
+int attn_decode_gqa_nsplit(int Skv, int Hkv, int D);
+// As launch_attn_decode, one block per KV head and chunk: q, o [B,1,Hq,D]
+// bf16; k, v rows of Hkv*D elements, Skv rows per batch entry, batch stride
+// Skv*Hkv*D (any stride when B == 1); q, k, v 16-byte aligned; lse [B,Hq]
+// f32; part [B*Hq, attn_decode_gqa_nsplit(Skv, Hkv, D), D+2] f32.
+// gqa_decode_supported(Hq, Hkv, D), Skv >= 1. len_dev: nullptr (all Skv
+// rows live), one int32, or B of them when len_stride; read on the device
+// and clamped to Skv there, <= 0 gives o = 0.
+void launch_attn_decode_gqa(const void* q, const void* k, const void* v,
+                            const int* len_dev, float* part, void* o,
+                            float* lse, int B, int Hq, int Hkv, int Skv,
+                            int D, float scale, int len_stride,
+                            hipStream_t st);
+
 // -------------------------------------------------------------------- kvq.hip
 // int8 KV cache: k8, v8 [Bc, max_s, Hkv, D] int8, ks, vs [Bc, Hkv, max_s]
 // f32 (one scale per token and kv head). D is 64 or 128, anything else
