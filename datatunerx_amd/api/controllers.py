@@ -492,6 +492,11 @@ class FinetuneJobController:
                 # quantized (int8/int4), as the job trained against it;
                 # admission rejects it together with tensorParallel > 1
                 args += ["--quantization", str(serve_cfg["quantization"])]
+            if serve_cfg.get("speculative"):
+                # serveConfig.speculative: draft tokens per decode step
+                # (prompt lookup); admission rejects it together with
+                # tensorParallel > 1
+                args += ["--speculative", str(serve_cfg["speculative"])]
             if ck.get("checkpointPath"):
                 args += ["--adapter", ck["checkpointPath"]]
             base_env = {"PYTHONPATH": self.cfg.repo_root,

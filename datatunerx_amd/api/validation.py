@@ -100,6 +100,15 @@ def validate_(obj: ApiObject) -> None:
             _require(not (isinstance(tp, int) and tp > 1),
                      "spec.serveConfig.quantization is not supported "
                      "with tensorParallel > 1", errs)
+        spec_k = sc.get("speculative")
+        if spec_k is not None:
+            _require(isinstance(spec_k, int) and
+                     not isinstance(spec_k, bool) and 0 <= spec_k <= 15,
+                     "spec.serveConfig.speculative must be an int in "
+                     "[0, 15] (draft tokens per decode step)", errs)
+            _require(not (spec_k and isinstance(tp, int) and tp > 1),
+                     "spec.serveConfig.speculative is not supported "
+                     "with tensorParallel > 1", errs)
         tmpl = sc.get("template")
         if tmpl is not None:
             from ..data.templates import TEMPLATES

@@ -182,6 +182,18 @@ def attn_fwd(q, k, v, causal: bool = True, scale: float | None = None,
             if _gqa_decode_ok(q, k):
                 return _EXT.attn_decode_gqa(q, k, v, scale, len_dev)
             return _EXT.attn_decode(q, k, v, scale, len_dev)
+        if len_dev is not None:
+            # a multi-token step over the cache (speculative verify): the
+            # only S > 1 kernel that reads the live length on the device
+            if not causal or q.dim() != 4 or k.dim() != 4 or \
+                    not _EXT.attn_verify_supported(
+                        q.shape[1], q.shape[2], k.shape[2], q.shape[3]):
+                raise ValueError(
+                    "attn_fwd: S > 1 with len_dev needs causal attention "
+                    "inside attn_verify_supported (D 64 or 128, S <= 16, "
+                    f"S * Hq / Hkv <= 32), got q {tuple(q.shape)}, "
+                    f"k {tuple(k.shape)}")
+            return _EXT.attn_verify(q, k, v, scale, len_dev)
         # V consumed row-major (PV B-frags via ds_read_b64_tr_b16):
         # no V pre-transpose
         return _EXT.attn_fwd(q, k, v.contiguous(), causal, scale)
@@ -252,6 +264,44 @@ def attn_decode_gqa(q, k, v, scale: float | None = None, len_dev=None):
             raise ValueError("attn_decode_gqa: len_dev must be [1] or [B]")
         len_dev = len_dev.clamp(max=k.shape[1])
     return _attn_fwd_cpu(q, k, v, False, scale, len_dev)
+
+
+def attn_verify_supported(T: int, Hq: int, Hkv: int, D: int) -> bool:
+    """Shapes the multi-token verify kernel takes (attn_verify.hip):
+    head_dim 64 or 128, Hq % Hkv == 0, 1 <= T <= 16 query rows and
+    T * Hq / Hkv <= 32. The predicate is the extension's own (the one its
+    binding checks)."""
+    ext = _load_ext()
+    if ext is None:
+        raise RuntimeError("attn_verify_supported needs the HIP extension "
+                           f"(_dtx_hip): {_EXT_ERR}")
+    return bool(ext.attn_verify_supported(T, Hq, Hkv, D))
+
+
+def attn_verify(q, k, v, scale: float | None = None, len_dev=None):
+    """Attention of the T new tokens of a decode step, q [B,T,Hq,D], over
+    the bf16 KV cache k, v [B,cap,Hkv,D] that already holds their rows ->
+    (o [B,T,Hq,D], lse [B,Hq,T]). len_dev (int32 [1] or [B], read on the
+    device and clamped to cap) is the live length INCLUDING the T rows;
+    without it every row of k is live (the B == 1 prefix view). Query t of
+    row b sees kv rows j <= len[b] - T + t. A row with fewer than T live
+    rows is the caller's error: the kernel gives the queries that see
+    nothing o = 0, the CPU reference raises. Needs
+    attn_verify_supported(T, Hq, Hkv, D). ops.attn_fwd routes here for
+    S > 1 with len_dev."""
+    if scale is None:
+        scale = 1.0 / (q.shape[-1] ** 0.5)
+    if _gpu(q):
+        return _EXT.attn_verify(q, k, v, scale, len_dev)
+    if q.dim() != 4:
+        raise ValueError("attn_verify: q must be [B,T,Hq,D]")
+    B, cap = q.shape[0], k.shape[1]
+    lens = [cap] * B
+    if len_dev is not None:
+        if len_dev.numel() not in (1, B):
+            raise ValueError("attn_verify: len_dev must be [1] or [B]")
+        lens = [min(int(n), cap) for n in len_dev.expand(B).tolist()]
+    return ref.attn_verify(q, k, v, scale, lens)
 
 
 def attn_bwd(q, k, v, o, do, lse, causal: bool = True,

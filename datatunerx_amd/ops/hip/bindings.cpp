@@ -908,6 +908,52 @@ std::vector<Tensor> attn_decode_gqa(Tensor q, Tensor k, Tensor v,
   return attn_decode_any("attn_decode_gqa", true, q, k, v, scale, len_dev);
 }
 
+// Multi-token verify attention (attn_verify.hip): q [B,T,Hq,D] over a cache
+// that already holds the T new rows, query t of row b seeing kv rows
+// j <= len[b] - T + t. k, v and len_dev as attn_decode_gqa takes them
+// (len_dev: the live length including the T rows; without it all Skv rows
+// of the B == 1 prefix view). Returns o [B,T,Hq,D] and lse [B,Hq,T], a
+// transposed view of the [B,T,Hq] buffer the combine kernel fills.
+std::vector<Tensor> attn_verify(Tensor q, Tensor k, Tensor v, double scale,
+                                OptTensor len_dev) {
+  const Op op("attn_verify", q, BF16, "q");
+  TORCH_CHECK(q.dim() == 4, "attn_verify: q must be [B,T,Hq,D]");
+  const int B = i32(q.size(0)), T = i32(q.size(1)), Hq = i32(q.size(2)),
+            D = i32(q.size(3));
+  TORCH_CHECK(op.dev(k, BF16, "k").dim() == 4 && k.size(0) == B &&
+              k.size(3) == D, "attn_verify: k must be [B,Skv,Hkv,D]");
+  op.shape(op.dev(v, BF16, "v"), k.sizes(), "v");
+  const int Skv = i32(k.size(1)), Hkv = i32(k.size(2));
+  TORCH_CHECK(Skv >= 1 && Hkv >= 1, "attn_verify: Skv >= 1, Hkv >= 1");
+  TORCH_CHECK(attn_verify_supported(T, Hq, Hkv, D),
+              "attn_verify: D in {64, 128}, Hq % Hkv == 0, 1 <= T <= 16 and "
+              "T * Hq / Hkv <= 32, got T = ", T, ", Hq = ", Hq, ", Hkv = ",
+              Hkv, ", D = ", D);
+  auto dense_kv = [&](const Tensor& t, const char* n) {
+    TORCH_CHECK(t.stride(3) == 1 && t.stride(2) == D &&
+                t.stride(1) == (long)Hkv * D, n, " must be s/h/d-dense");
+    if (B > 1) op.dense(t, BF16, n);
+  };
+  dense_kv(k, "k");
+  dense_kv(v, "v");
+  op.aligned16("q, k, v", {q.data_ptr(), k.data_ptr(), v.data_ptr()});
+  const int* ld = op.opt<int>(len_dev, I32, "len_dev");
+  TORCH_CHECK(!ld || len_dev->numel() == 1 || len_dev->numel() == B,
+              "len_dev must be [1] or [B]");
+  const int len_stride = ld && len_dev->numel() > 1;
+  auto o = torch::empty_like(q);
+  auto lse = torch::empty({B, T, Hq}, q.options().dtype(F32));
+  if (B == 0) return {o, lse.transpose(1, 2)};
+  auto part = torch::empty(
+      {(long)B * T * Hq, attn_verify_nsplit(Skv, Hkv, D), D + 2},
+      lse.options());
+  launch_attn_verify(q.data_ptr(), k.data_ptr(), v.data_ptr(), ld,
+                     part.data_ptr<float>(), o.data_ptr(),
+                     lse.data_ptr<float>(), B, T, Hq, Hkv, Skv, D,
+                     (float)scale, len_stride, op.stream);
+  return {o, lse.transpose(1, 2)};
+}
+
 // ------------------------------------------------------ int8 KV cache
 // k8, v8 [Bc, max_s, Hkv, D] int8 and ks, vs [Bc, Hkv, max_s] f32
 // (kvq.hip): the cache's shape, D in {64, 128}.
@@ -1126,6 +1172,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_decode_gqa_chunk", &attn_decode_gqa_chunk, py::arg("skv"),
         py::arg("hkv"), py::arg("d"));
   m.def("attn_decode_gqa_nsplit", &attn_decode_gqa_nsplit, py::arg("skv"),
+        py::arg("hkv"), py::arg("d"));
+  m.def("attn_verify", &attn_verify, py::arg("q"), py::arg("k"),
+        py::arg("v"), py::arg("scale"), py::arg("len_dev") = py::none());
+  m.def("attn_verify_supported", &attn_verify_supported, py::arg("t"),
+        py::arg("hq"), py::arg("hkv"), py::arg("d"));
+  m.def("attn_verify_chunk", &attn_verify_chunk, py::arg("skv"),
+        py::arg("hkv"), py::arg("d"));
+  m.def("attn_verify_nsplit", &attn_verify_nsplit, py::arg("skv"),
         py::arg("hkv"), py::arg("d"));
   m.def("kv_quant_append", &kv_quant_append, py::arg("k"), py::arg("v"),
         py::arg("k8"), py::arg("v8"), py::arg("ks"), py::arg("vs"),

@@ -177,6 +177,29 @@ void launch_attn_decode_gqa(const void* q, const void* k, const void* v,
                             int D, float scale, int len_stride,
                             hipStream_t st);
 
+// ------------------------------------------------------------ attn_verify.hip
+// Shapes the multi-token verify kernel takes: D in {64, 128}, Hq % Hkv ==
+// 0, 1 <= T <= 16 query rows a sequence and T * (Hq / Hkv) <= 32 MFMA
+// columns a kv head. The one predicate: the binding checks it and Python
+// routes by it.
+bool attn_verify_supported(int T, int Hq, int Hkv, int D);
+// Split plan (attn_decode_gqa's): rows per chunk and chunks = planes of the
+// part workspace; a function of the addressed capacity and the head shape.
+int attn_verify_chunk(int Skv, int Hkv, int D);
+int attn_verify_nsplit(int Skv, int Hkv, int D);
+// q, o [B,T,Hq,D] bf16; k, v as launch_attn_decode_gqa, holding the T new
+// rows already; lse [B,T,Hq] f32; part [B*T*Hq, attn_verify_nsplit(Skv,
+// Hkv, D), D+2] f32. attn_verify_supported(T, Hq, Hkv, D), Skv >= 1.
+// len_dev: nullptr (all Skv rows live), one int32, or B of them when
+// len_stride: the live length INCLUDING the T rows, read on the device and
+// clamped to Skv there. Query t sees rows j <= len - T + t; a query with a
+// negative limit (len < T) gets o = 0.
+void launch_attn_verify(const void* q, const void* k, const void* v,
+                        const int* len_dev, float* part, void* o,
+                        float* lse, int B, int T, int Hq, int Hkv, int Skv,
+                        int D, float scale, int len_stride,
+                        hipStream_t st);
+
 // -------------------------------------------------------------------- kvq.hip
 // int8 KV cache: k8, v8 [Bc, max_s, Hkv, D] int8, ks, vs [Bc, Hkv, max_s]
 // f32 (one scale per token and kv head). D is 64 or 128, anything else

@@ -183,6 +183,23 @@ def attn_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
     return o.permute(0, 2, 1, 3).contiguous(), lse
 
 
+def attn_verify(q, k, v, scale, lens):
+    """Multi-token verify attention: q [B,T,Hq,D] over a cache k, v
+    [B,cap,Hkv,D] that holds the T new rows already; lens[b] live rows
+    including them. Query t of row b sees rows j <= lens[b] - T + t: causal
+    attention, bottom-right aligned, over the live prefix of each row."""
+    outs, lses = [], []
+    for b, n in enumerate(lens):
+        if n < q.shape[1]:
+            raise ValueError(f"attn_verify: row {b} has {n} live rows for "
+                             f"{q.shape[1]} queries")
+        o, lse = attn_fwd(q[b:b + 1], k[b:b + 1, :n], v[b:b + 1, :n], True,
+                          scale)
+        outs.append(o)
+        lses.append(lse)
+    return torch.cat(outs, 0), torch.cat(lses, 0)
+
+
 def attn_bwd(q, k, v, o, do, lse, causal: bool = True,
              scale: float | None = None, doc_start=None):
     """BSHD public contract; returns (dq, dk, dv) in BSHD."""

@@ -32,7 +32,7 @@ class KVCache:
     """BSHD cache ([B, max_s, Hkv, D]) matching the attention kernels'
     native layout — appends along dim 1.
 
-    update() returns (k, v, len_dev) in one of two modes. Host mode (no
+    update() returns (k, v, len_dev) in one of three modes. Host mode (no
     counters, or S > 1): append at the host counter `cur`; the returned
     tensors are the length-exact prefix and len_dev is None. Device mode
     (counters given and S == 1): one token per row written at wpos[b];
@@ -41,25 +41,45 @@ class KVCache:
     value enters the step, so it replays from a hipGraph. wpos (int64
     [B], an index into the cache flattened to [B * max_s] slots) and
     len32 (int32 [B]) belong to a _DecodeState and are shared by every
-    layer's cache."""
+    layer's cache.
+
+    Device mode, T tokens per row (a verify step of speculative decoding):
+    chosen by the decode state, which hands the cache `wslots` (int64
+    [B * T], row b's flat slots wpos[b] .. wpos[b] + T - 1), never inferred
+    from S: a right-padded batched prefill is S > 1 with counters present
+    and stays in host mode. Every update must then bring exactly T rows;
+    they go to their slots in one index_copy_ per tensor, the returned
+    tensors are full-capacity and len32 counts the T rows as live. The
+    state keeps the slots inside the cache."""
 
     def __init__(self, B, Hkv, max_s, D, device, dtype,
-                 wpos=None, len32=None):
+                 wpos=None, len32=None, wslots=None):
         self.k = torch.zeros(B, max_s, Hkv, D, device=device, dtype=dtype)
         self.v = torch.zeros(B, max_s, Hkv, D, device=device, dtype=dtype)
         self.cur = 0
-        self.wpos, self.len32 = wpos, len32
+        self.wpos, self.len32, self.wslots = wpos, len32, wslots
 
     def row_view(self, i):
         """Host-mode B = 1 cache over row i's storage: ragged rows
         prefill one at a time through it."""
         row = copy.copy(self)
         row.k, row.v = self.k[i:i + 1], self.v[i:i + 1]
-        row.cur, row.wpos, row.len32 = 0, None, None
+        row.cur, row.wpos, row.len32, row.wslots = 0, None, None, None
         return row
 
     def update(self, k, v):
         S = k.shape[1]
+        if self.wslots is not None:
+            if k.shape[0] * S != self.wslots.numel():
+                raise ValueError(
+                    f"KVCache: a {self.wslots.numel()}-slot verify cache "
+                    f"got an update of {k.shape[0]} x {S} rows (prefill "
+                    "through row_view)")
+            self.k.view(-1, *k.shape[2:]).index_copy_(
+                0, self.wslots, k.reshape(-1, *k.shape[2:]))
+            self.v.view(-1, *v.shape[2:]).index_copy_(
+                0, self.wslots, v.reshape(-1, *v.shape[2:]))
+            return self.k, self.v, self.len32
         if self.wpos is not None and S == 1:
             # one flat index_copy_ for every B: an advanced-index put at
             # (row, pos) costs single-stream decode 2 % (64 writes a
@@ -159,15 +179,27 @@ class _DecodeState:
     The rows' sampling parameters are device state too (temperature,
     top_p, top_k, seed, and offset: the number of tokens the row has
     sampled, its RNG counter), so ops.sample draws every row of a step
-    with that row's own setting; all-zero (the start) is greedy."""
+    with that row's own setting; all-zero (the start) is greedy.
+
+    width > 1 makes it the state of verify steps (speculative decoding):
+    a step carries `width` tokens per row, written at pos[b] ..
+    pos[b] + width - 1 (`wslots`, the caches' multi-token device mode) and
+    counted live, len32 == pos + width; advance(n) then keeps the first n
+    of them. The caller keeps pos + width <= max_s."""
 
     def __init__(self, B, Hkv, max_s, D, layers, device, dtype,
-                 kv_cache="bf16"):
-        self.B, self.max_s = B, max_s
+                 kv_cache="bf16", width=1):
+        self.B, self.max_s, self.width = B, max_s, width
         self._row0 = torch.arange(B, device=device) * max_s
         self.wpos = self._row0.clone()
         self.pos32 = torch.zeros(B, dtype=torch.int32, device=device)
-        self.len32 = torch.ones(B, dtype=torch.int32, device=device)
+        self.len32 = torch.full((B,), width, dtype=torch.int32,
+                                device=device)
+        kw = {}
+        if width > 1:
+            self._slot0 = torch.arange(width, device=device).repeat(B)
+            self.wslots = self.wpos.repeat_interleave(width) + self._slot0
+            kw["wslots"] = self.wslots
         self.temperature = torch.zeros(B, dtype=torch.float32,
                                        device=device)
         self.top_p = torch.ones(B, dtype=torch.float32, device=device)
@@ -176,7 +208,7 @@ class _DecodeState:
         self.offset = torch.zeros(B, dtype=torch.int32, device=device)
         cache = _kv_cache_class(kv_cache)
         self.caches = [cache(B, Hkv, max_s, D, device, dtype,
-                             wpos=self.wpos, len32=self.len32)
+                             wpos=self.wpos, len32=self.len32, **kw)
                        for _ in range(layers)]
 
     def set_state(self, lens):
@@ -185,7 +217,10 @@ class _DecodeState:
                            device=self.wpos.device)
         self.wpos.copy_(self._row0 + pos)
         self.pos32.copy_(pos)
-        self.len32.copy_(pos + 1)
+        self.len32.copy_(pos + self.width)
+        if self.width > 1:
+            self.wslots.copy_(self.wpos.repeat_interleave(self.width) +
+                              self._slot0)
 
     def set_sampling(self, samp, offset: int = 1):
         """Per-row sampling parameters (a _Sampling of B rows). offset:
@@ -209,11 +244,16 @@ class _DecodeState:
         for c in self.caches:
             c.cur = 0
 
-    def advance(self):
-        self.wpos += 1
-        self.pos32 += 1
-        self.len32 += 1
-        self.offset += 1
+    def advance(self, n: int = 1):
+        """Every row keeps n more tokens (n < width: the rows of a verify
+        step past the n-th stay in the cache beyond the next step's reach
+        and are overwritten by it)."""
+        self.wpos += n
+        self.pos32 += n
+        self.len32 += n
+        self.offset += n
+        if self.width > 1:
+            self.wslots += n
 
 
 class _GraphedDecoder(_DecodeState):
@@ -227,20 +267,30 @@ class _GraphedDecoder(_DecodeState):
     [B, 1, V] and `out` [B]: the greedy argmax, or with `sample` the
     token ops.sample draws for each row from the state's sampling
     buffers (a row at temperature 0 gets the same argmax, bit for bit),
-    so one graph serves every mix of greedy and sampled rows."""
+    so one graph serves every mix of greedy and sampled rows.
+
+    width = T > 1 captures a verify step instead (B == 1, greedy): the
+    input is [1, T], `logits` [1, T, V] and `out` [T], the argmax after
+    each of the T tokens; step() does not advance, the caller keeps as
+    many tokens as it accepted (advance(n))."""
 
     def __init__(self, model, cfg, device, B, max_s, sample=False,
-                 kv_cache="bf16"):
+                 kv_cache="bf16", width=1):
+        if width > 1 and (B != 1 or sample or max_s < width):
+            raise ValueError("a verify decoder is one greedy row of at "
+                             "least `width` positions")
         super().__init__(B, cfg.num_key_value_heads, max_s, cfg.head_dim,
                          cfg.num_hidden_layers, device,
-                         next(model.parameters()).dtype, kv_cache)
-        self.input = torch.ones(B, 1, dtype=torch.long, device=device)
+                         next(model.parameters()).dtype, kv_cache, width)
+        self.input = torch.ones(B, width, dtype=torch.long, device=device)
         # -1 = base model / dummy row
         self.adapter_idx, akw = _graph_adapter_buffer(model, B, device)
 
         def forward():
             logits = model(self.input, pos_dev=self.pos32,
                            kv_caches=self.caches, **akw)
+            if width > 1:
+                return logits, logits[0].argmax(-1)
             if sample:
                 from .. import ops
                 return logits, ops.sample(logits[:, -1],
@@ -262,10 +312,12 @@ class _GraphedDecoder(_DecodeState):
 
     def step(self, cur):
         """cur: this step's input tokens — [B, 1] int64 on device, or a
-        host int when B == 1. Refreshes `logits` and `out`."""
+        host int when B == 1 ([1, T] for a verify decoder). Refreshes
+        `logits` and `out`."""
         self.input[:] = cur
         self.graph.replay()
-        self.advance()
+        if self.width == 1:
+            self.advance()
 
 
 def builtin_config(name: str, **lora_kw):
@@ -424,9 +476,18 @@ class InferenceEngine:
 
     def __init__(self, model, tokenizer=None, template: str = "llama2",
                  device=None, graph_decode: bool = True,
-                 own_stream: bool = False, kv_cache: str = "bf16"):
+                 own_stream: bool = False, kv_cache: str = "bf16",
+                 speculative: int = 0):
         """kv_cache: "bf16", or "int8" for the quantized KV cache (llama
-        models inside ops.kv_int8_supported, one GPU or the CPU)."""
+        models inside ops.kv_int8_supported, one GPU or the CPU).
+        speculative: K in 0..15 draft tokens per step for single-stream
+        requests at temperature 0 (prompt-lookup drafts verified K + 1
+        tokens at a time, serve/lookup.py); 0 leaves every path as it is.
+        Llama models over the bf16 cache on one device. On the GPU the
+        engine then holds two graphed decoders at full context, the
+        verify decoder and the single-token one sampled requests use,
+        each with a KV cache of its own (llama2-7b at 4096 positions:
+        2 GiB each)."""
         self.model = model
         self.tok = tokenizer or ByteTokenizer()
         self.template = template
@@ -434,9 +495,16 @@ class InferenceEngine:
         self.is_llama = isinstance(model, LlamaForCausalLM)
         _kv_cache_class(kv_cache)
         self.kv_cache = kv_cache
+        self.speculative = self._check_speculative(speculative)
         if kv_cache == "int8":
             self._check_kv_int8()
         import torch.distributed as dist
+        # verify steps run and tokens accepted out of them (per step the
+        # kept drafts and the step's own token; where a stop id or the
+        # budget ends the request mid-step, the rest of that step's
+        # tokens is counted and never sent)
+        self.spec_stats = {"verify_steps": 0, "tokens": 0}
+        self._vgraphed = None
         self._graphed = None
         self._bgraphed = None
         self._stream = (torch.cuda.Stream(device=self.device)
@@ -492,6 +560,40 @@ class InferenceEngine:
                 f"heads, {cfg.num_key_value_heads} kv heads, head_dim "
                 f"{cfg.head_dim}")
 
+    def _check_speculative(self, k) -> int:
+        """The speculative-decoding switch, checked before any allocation."""
+        import torch.distributed as dist
+        k = int(k or 0)
+        if not 0 <= k <= 15:
+            raise ValueError(f"speculative must be in 0..15 draft tokens "
+                             f"per step, got {k}")
+        if k == 0:
+            return 0
+        if not self.is_llama:
+            raise ValueError("speculative decoding supports llama models "
+                             "only")
+        if self.kv_cache != "bf16":
+            raise ValueError(
+                "speculative decoding needs kv_cache='bf16': a verify step "
+                f"over the {self.kv_cache} KV cache (attention over a "
+                "quantized prefix) is not supported")
+        if dist.is_initialized() and dist.get_world_size() > 1:
+            raise ValueError("speculative decoding is single-device: it "
+                             "cannot be combined with tensor parallelism")
+        cfg = self.model.cfg
+        if self.device.type == "cuda":
+            from .. import ops
+            if not ops.attn_verify_supported(
+                    k + 1, cfg.num_attention_heads, cfg.num_key_value_heads,
+                    cfg.head_dim):
+                raise ValueError(
+                    f"speculative={k}: {k + 1} tokens a step of "
+                    f"{cfg.num_attention_heads} heads over "
+                    f"{cfg.num_key_value_heads} kv heads, head_dim "
+                    f"{cfg.head_dim}, is outside ops.attn_verify_supported "
+                    "(head_dim 64 or 128, (K + 1) * Hq / Hkv <= 32)")
+        return k
+
     # ---------------------------------------------------- adapters
     def _adapter_index(self, adapter: Optional[str]) -> int:
         """Registry index of a request's adapter (-1: base model).
@@ -531,17 +633,28 @@ class InferenceEngine:
     # distinct graphs on distinct streams are concurrency-safe.
     _capture_lock = __import__("threading").Lock()
 
-    def _capture(self, B, max_s):
+    def _capture(self, B, max_s, width=1):
         """A new graphed decoder, or None when its capture fails (the
-        caller decides what that turns off)."""
+        caller decides what that turns off). width > 1: a verify
+        decoder, greedy."""
         try:
             with InferenceEngine._capture_lock, self._stream_ctx():
-                return _GraphedDecoder(self.model, self.model.cfg,
-                                       self.device, B, max_s,
-                                       sample=self.device_sampling,
-                                       kv_cache=self.kv_cache)
+                return _GraphedDecoder(
+                    self.model, self.model.cfg, self.device, B, max_s,
+                    sample=self.device_sampling and width == 1,
+                    kv_cache=self.kv_cache, width=width)
         except Exception:
             return None
+
+    def _get_verify_graphed(self):
+        """The verify decoder of speculative decoding (K + 1 tokens a
+        step) at full context; a failed capture leaves verify steps eager
+        (`_vgraphed` False: not tried again)."""
+        if self._vgraphed is None and self._graph_ok:
+            self._vgraphed = self._capture(
+                1, self.model.cfg.max_position_embeddings,
+                self.speculative + 1) or False
+        return self._vgraphed or None
 
     def _get_graphed(self):
         """Single-stream decoder at full context; a failed capture turns
@@ -567,6 +680,7 @@ class InferenceEngine:
         with self._stream_ctx():
             self._get_graphed()
             list(self.generate([1], max_new_tokens=2))
+        self.spec_stats.update(verify_steps=0, tokens=0)    # not traffic
         if self.device.type == "cuda":
             torch.cuda.synchronize()
 
@@ -716,6 +830,10 @@ class InferenceEngine:
                 f"context ({limit} positions)")
         ids = torch.tensor([prompt_ids], dtype=torch.long,
                            device=self.device)
+        if self.speculative and samp.greedy:
+            yield from self._generate_speculative(prompt_ids, ids,
+                                                  max_new_tokens, gi, akw)
+            return
         dev = self.device_sampling
 
         def pick(logits, n):        # logits [1, S, V] -> token n
@@ -782,6 +900,103 @@ class InferenceEngine:
                     break
                 yield nxt
                 seq.append(nxt)
+
+    def _verify_state(self, n_prompt: int, max_new_tokens: int):
+        """Decode state of a speculative request: the graphed verify
+        decoder where there is one and the prompt leaves it a step, else
+        eager state sized for the request."""
+        T = self.speculative + 1
+        gd = self._get_verify_graphed()
+        if gd is not None and n_prompt + T <= gd.max_s:
+            return gd
+        cfg = self.model.cfg
+        max_s = min(cfg.max_position_embeddings,
+                    n_prompt + max_new_tokens + T + 8)
+        return _DecodeState(1, cfg.num_key_value_heads, max_s,
+                            cfg.head_dim, cfg.num_hidden_layers,
+                            self.device,
+                            next(self.model.parameters()).dtype,
+                            self.kv_cache, width=T)
+
+    def _generate_speculative(self, prompt_ids, ids, max_new_tokens,
+                              gi, akw):
+        """Greedy single-stream decoding, K + 1 tokens a step. A step's
+        input is the last token and K prompt-lookup drafts (padded with
+        token 0: a pad is a draft like any other, kept only if it IS the
+        argmax); its output the argmax after each of them. Draft i is
+        kept while it equals the argmax after its predecessor, and the
+        argmax after the last kept token is the step's own token: the
+        tokens are those of one-token greedy decoding as far as the two
+        computations agree on every argmax. The rows of rejected drafts
+        stay in the cache past the live length; the next step overwrites
+        them. Verify steps run while pos + K + 1 <= max_s, single-token
+        eager steps finish the tail, so nothing is written outside the
+        cache."""
+        from .lookup import prompt_lookup
+        K = self.speculative
+        T = K + 1
+        st = self._verify_state(len(prompt_ids), max_new_tokens)
+        graphed = isinstance(st, _GraphedDecoder)
+        st.reset()
+        if graphed:
+            st.set_adapters([gi])
+        # prefill in host mode, through the B = 1 views of the caches
+        rows = [c.row_view(0) for c in st.caches]
+        logits = self.model(ids, pos0=0, kv_caches=rows, **akw)
+        pos = len(prompt_ids)       # tokens in the cache
+        st.set_state([pos])
+        nxt = int(logits[0, -1].argmax())
+        seq = list(prompt_ids)
+        n_out = 0
+
+        def emit(tok):              # -> the request goes on
+            nonlocal n_out
+            seq.append(tok)
+            n_out += 1
+            return n_out < max_new_tokens
+
+        while pos + T <= st.max_s:
+            if self._is_stop(nxt):
+                return
+            yield nxt
+            if not emit(nxt):
+                return
+            draft = prompt_lookup(seq, K)
+            toks = torch.tensor([[nxt] + draft + [0] * (K - len(draft))],
+                                dtype=torch.long)
+            if graphed:
+                st.step(toks)
+                out = st.out.tolist()           # the step's one host read
+            else:
+                out = self.model(
+                    toks.to(self.device), pos_dev=st.pos32,
+                    kv_caches=st.caches, **akw)[0].argmax(-1).tolist()
+            kept = 0
+            while kept < K and int(toks[0, kept + 1]) == out[kept]:
+                kept += 1
+            self.spec_stats["verify_steps"] += 1
+            self.spec_stats["tokens"] += kept + 1
+            st.advance(kept + 1)
+            pos += kept + 1
+            for tok in out[:kept]:              # the kept drafts
+                if self._is_stop(tok):
+                    return
+                yield tok
+                if not emit(tok):
+                    return
+            nxt = out[kept]
+        # the tail: single-token steps in host mode over the same rows
+        for c in rows:
+            c.cur = pos
+        while not self._is_stop(nxt):
+            yield nxt
+            if not emit(nxt) or pos + 1 >= st.max_s:
+                return
+            cur = torch.tensor([[nxt]], dtype=torch.long,
+                               device=self.device)
+            logits = self.model(cur, pos0=pos, kv_caches=rows, **akw)
+            pos += 1
+            nxt = int(logits[0, -1].argmax())
 
     def _sample(self, logits: torch.Tensor, temperature: float,
                 top_p: float, top_k: int = 0, seed: Optional[int] = None,

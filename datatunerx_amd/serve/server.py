@@ -31,18 +31,30 @@ class EnginePool:
     def __init__(self, engines):
         import queue
         self._q = queue.Queue()
-        for e in engines:
+        self._engines = list(engines)
+        for e in self._engines:
             try:
                 e.warmup()
             except Exception:
                 pass
             self._q.put(e)
 
+    @property
+    def engines(self):
+        return tuple(self._engines)
+
     def acquire(self):
         return self._q.get()
 
     def release(self, e):
         self._q.put(e)
+
+
+def spec_stats(engines):
+    """The speculative-decoding counters summed over the engines that
+    speculate ({} when none does)."""
+    on = [e.spec_stats for e in engines if getattr(e, "speculative", 0)]
+    return {k: sum(s[k] for s in on) for k in (on[0] if on else ())}
 
 
 class BatchingFront:
@@ -208,6 +220,9 @@ def build_handler(pool, batcher=None, model_name: str = "datatunerx",
         pool = EnginePool([pool])
     multi = adapter_names is not None
     adapter_names = tuple(adapter_names or ())
+    # the engines chat requests run on: the batcher's when there is one
+    # (the pool then serves /score only), else the pool's
+    generators = (batcher.engine,) if batcher is not None else pool.engines
 
     class _UnknownModel(Exception):
         pass
@@ -266,7 +281,9 @@ def build_handler(pool, batcher=None, model_name: str = "datatunerx",
 
         def do_GET(self):
             if self.path == "/health":
-                self._send(200, {"status": "ok"})
+                # with --speculative: verify_steps and tokens so far,
+                # over every engine that generates
+                self._send(200, {"status": "ok", **spec_stats(generators)})
             elif self.path in ("/v1/models", "/models"):
                 # OpenAI-SDK discovery call (clients list models first)
                 self._send(200, {"object": "list", "data": [{
@@ -504,6 +521,11 @@ def parse_args(argv=None):
                     help="KV cache format; int8 halves the cache and its "
                          "decode traffic (single-GPU llama models inside "
                          "ops.kv_int8_supported)")
+    ap.add_argument("--speculative", type=int, default=0, metavar="K",
+                    help="speculative decoding of single-stream requests "
+                         "at temperature 0: K prompt-lookup draft tokens "
+                         "verified per step, 0..15 (single-GPU llama "
+                         "models over the bf16 KV cache); 0: off")
     args = ap.parse_args(argv)
     args.adapter, args.adapters = _split_adapters(ap, args.adapter)
     return args
@@ -607,6 +629,64 @@ def _check_kv_cache(args, world: int):
                 f"128 and a GQA group of at most 16, not {args.model!r}")
 
 
+def _check_speculative(args, world: int):
+    """--speculative is refused at start-up where it cannot be honoured
+    rather than silently decoding one token a step."""
+    if not args.speculative:
+        return
+    if not 0 < args.speculative <= 15:
+        raise SystemExit(
+            f"--speculative takes 0..15 draft tokens, not {args.speculative}")
+    if world > 1:
+        raise SystemExit(
+            "--speculative is not supported with tensor-parallel serving "
+            f"(WORLD_SIZE={world}); serve it on one GPU")
+    if args.kv_cache != "bf16":
+        raise SystemExit(
+            f"--speculative is not supported with --kv-cache {args.kv_cache}"
+            ": a verify step needs attention over the cached prefix, which "
+            "only the bf16 cache has")
+    from .engine import builtin_config
+    from ..models.hf_io import is_hf_model_dir
+    if not is_hf_model_dir(args.model):
+        try:
+            family, _ = builtin_config(args.model)
+        except ValueError as e:
+            raise SystemExit(str(e))
+        if family != "llama":
+            raise SystemExit(
+                f"--speculative supports llama models, not {args.model!r}")
+
+
+def build_fronts(model, tok, args, device):
+    """(pool, batcher) of the single-GPU service. With a batcher (llama
+    models unless DTX_SERVE_BATCH=0) every chat request runs on the
+    batcher's engine, a lone one on its single-stream path, and the pool
+    serves /score only. --speculative therefore goes to the engines that
+    generate: the batcher's when there is one, else the pool's. The others
+    capture no verify decoder and hold no cache for one."""
+    from ..models import LlamaForCausalLM
+    from .engine import InferenceEngine
+    batching = os.environ.get("DTX_SERVE_BATCH", "1") != "0" and \
+        isinstance(model, LlamaForCausalLM)
+    n_slots = max(1, int(os.environ.get("DTX_SERVE_CONCURRENCY", "2")))
+    pool = EnginePool([
+        InferenceEngine(model, tokenizer=tok, template=args.template,
+                        device=device, own_stream=(n_slots > 1),
+                        kv_cache=args.kv_cache,
+                        speculative=0 if batching else args.speculative)
+        for _ in range(n_slots)])
+    batcher = None
+    if batching:
+        batcher = BatchingFront(
+            InferenceEngine(model, tokenizer=tok, template=args.template,
+                            device=device, own_stream=True,
+                            kv_cache=args.kv_cache,
+                            speculative=args.speculative),
+            max_batch=int(os.environ.get("DTX_SERVE_MAX_BATCH", "8")))
+    return pool, batcher
+
+
 def main(argv=None):
     import os
 
@@ -614,6 +694,7 @@ def main(argv=None):
     args = parse_args(argv)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     _check_quantization(args, world)
+    _check_speculative(args, world)
     _check_kv_cache(args, world)
     _check_adapters(args, world)
     if world > 1:
@@ -668,7 +749,6 @@ def main(argv=None):
         else:
             tp_follower_loop(engine)
         return
-    from ..models import LlamaForCausalLM
     from ..models.hf_io import load_tokenizer
     device = torch.device("cuda:0" if torch.cuda.is_available() else "cpu")
     if args.adapters:
@@ -680,21 +760,8 @@ def main(argv=None):
     else:
         model = build_model(args.model, device, adapter_dir=args.adapter,
                             quantization=args.quantization)
-    tok = load_tokenizer(args.model)
-    n_slots = max(1, int(os.environ.get("DTX_SERVE_CONCURRENCY", "2")))
-    pool = EnginePool([
-        InferenceEngine(model, tokenizer=tok, template=args.template,
-                        device=device, own_stream=(n_slots > 1),
-                        kv_cache=args.kv_cache)
-        for _ in range(n_slots)])
-    batcher = None
-    if os.environ.get("DTX_SERVE_BATCH", "1") != "0" and \
-            isinstance(model, LlamaForCausalLM):
-        batcher = BatchingFront(
-            InferenceEngine(model, tokenizer=tok, template=args.template,
-                            device=device, own_stream=True,
-                            kv_cache=args.kv_cache),
-            max_batch=int(os.environ.get("DTX_SERVE_MAX_BATCH", "8")))
+    pool, batcher = build_fronts(model, load_tokenizer(args.model), args,
+                                 device)
     httpd = ThreadingHTTPServer((args.host, args.port),
                                 build_handler(
                                     pool, batcher, model_name=args.model,
