@@ -123,7 +123,9 @@ class FinetuneController:
             add("--packing", "true")          # sequence packing (sft | pt)
         add("--lr_scheduler_type", p.get("scheduler"))
         add("--optim", p.get("optimizer"))
-        if p.get("int4"):
+        if p.get("nf4"):
+            add("--quantization", "nf4")
+        elif p.get("int4"):
             add("--quantization", "int4")
         elif p.get("int8"):
             add("--quantization", "int8")

@@ -119,7 +119,7 @@ class Finetune(ApiObject):
 class FinetuneJob(ApiObject):
     """spec: fineTune{name, finetuneSpec}, scoringPluginConfig{name,
     parameters}, serveConfig{tensorParallel, template, quantization
-    (int8|int4, single-GPU serving only)}. status: state,
+    (int8|int4|nf4, single-GPU serving only)}. status: state,
     finetuneStatus, result{
     modelExportResult, image, serve, dashboard, score}, stats
     (finetunejob_controller.go:71-143)."""
@@ -147,7 +147,7 @@ class LLM(ApiObject):
 
 
 class Hyperparameter(ApiObject):
-    """spec.parameters: scheduler, optimizer, int4, int8, loRA_R,
+    """spec.parameters: scheduler, optimizer, int4, int8, nf4, loRA_R,
     loRA_Alpha, loRA_Dropout, learningRate, epochs, blockSize, batchSize,
     warmupRatio, weightDecay, gradAccSteps, trainerType, PEFT, FP16
     (finetune_controller.go:483-506); stage (sft | pt | dpo), dpoBeta,

@@ -94,9 +94,10 @@ def validate_(obj: ApiObject) -> None:
                  "[1, 8] (one 8-GPU MI355X node)", errs)
         quant = sc.get("quantization")
         if quant is not None:
-            _require(isinstance(quant, str) and quant in ("int8", "int4"),
-                     "spec.serveConfig.quantization must be int8 or int4",
-                     errs)
+            _require(isinstance(quant, str) and
+                     quant in ("int8", "int4", "nf4"),
+                     "spec.serveConfig.quantization must be int8, int4 "
+                     "or nf4", errs)
             _require(not (isinstance(tp, int) and tp > 1),
                      "spec.serveConfig.quantization is not supported "
                      "with tensorParallel > 1", errs)
@@ -156,8 +157,9 @@ def validate_(obj: ApiObject) -> None:
             _require(bs is None or (isinstance(bs, int) and
                                     not isinstance(bs, bool) and bs >= 1),
                      "spec.parameters.batchSize must be >= 1", errs)
-            _require(not (params.get("int4") and params.get("int8")),
-                     "int4 and int8 are mutually exclusive", errs)
+            _require(sum(bool(params.get(q))
+                         for q in ("int4", "int8", "nf4")) <= 1,
+                     "int4, int8 and nf4 are mutually exclusive", errs)
             st = params.get("stage")
             _require(st is None or st in ("sft", "pt", "dpo"),
                      "spec.parameters.stage must be sft, pt or dpo", errs)

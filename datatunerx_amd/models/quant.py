@@ -3,11 +3,16 @@ bitsandbytes int8/int4 path — cmd/tuning/train.py:224-234, Hyperparameter
 int4/int8 flags mapped at finetune_controller.go:486-494).
 
 MI355X-first design: with 288 GB HBM3E the capacity motivation is weak,
-so this is a fidelity feature — weights are stored quantized
-(int8 per-row absmax, or int4 group-64 absmax like nf4's grouping) and
+so this is a fidelity feature — weights are stored quantized and
 dequantized to the compute dtype on the fly; the LoRA low-rank path and
 all activations stay bf16. Dequant is one elementwise pass per forward
-(memory-bound, ~1% of the GEMM it feeds).
+(memory-bound, ~1% of the GEMM it feeds). Three formats:
+  int8  per-row absmax, 255 evenly spaced levels
+  int4  group-64 absmax, 15 evenly spaced levels
+  nf4   group-64 absmax, the 16 NormalFloat4 levels of QLoRA (what the
+        reference's bnb_4bit_quant_type="nf4" stores, without double
+        quantization): same bytes per weight as int4, ~0.86 of its rms
+        error on normal weights. Selected with bits=4, codebook="nf4".
 """
 
 from __future__ import annotations
@@ -54,17 +59,66 @@ def dequantize_int4(packed: torch.Tensor, scale: torch.Tensor, dtype,
     return q.view(N, K).to(dtype)
 
 
+# The 16 published NF4 levels (QLoRA), index 0..15, monotone, index 7 = 0.
+NF4_CODE = (
+    -1.0, -0.6961928009986877, -0.5250730514526367, -0.39491748809814453,
+    -0.28444138169288635, -0.18477343022823334, -0.09105003625154495, 0.0,
+    0.07958029955625534, 0.16093020141124725, 0.24611230194568634,
+    0.33791524171829224, 0.44070982933044434, 0.5626170039176941,
+    0.7229568362236023, 1.0)
+
+
+def quantize_nf4(w: torch.Tensor, group: int = 64):
+    """Group-wise absmax NF4: the index of the nearest level of
+    w / absmax (ties by torch.bucketize against the 15 midpoints), packed
+    two per byte like int4 (low nibble = even k). Returns
+    (packed [N,K/2] uint8, absmax [N,K/group] f32)."""
+    N, K = w.shape
+    assert K % group == 0, "K % group"
+    wf = w.float().view(N, K // group, group)
+    absmax = wf.abs().amax(dim=2).clamp(min=1e-8)          # [N, K/g]
+    code = torch.tensor(NF4_CODE, dtype=torch.float32, device=w.device)
+    idx = torch.bucketize(wf / absmax[:, :, None],
+                          (code[:-1] + code[1:]) / 2)
+    q = idx.to(torch.uint8).view(N, K)
+    packed = (q[:, 0::2] | (q[:, 1::2] << 4)).contiguous()  # [N, K/2]
+    return packed, absmax
+
+
+def dequantize_nf4(packed: torch.Tensor, absmax: torch.Tensor, dtype,
+                   group: int = 64):
+    """NF4_CODE[idx] * absmax in fp32, then one cast."""
+    N, K2 = packed.shape
+    K = K2 * 2
+    idx = torch.stack([packed & 0xF, packed >> 4], dim=2).view(N, K).long()
+    code = torch.tensor(NF4_CODE, dtype=torch.float32,
+                        device=packed.device)
+    q = code[idx].view(N, K // group, group) * absmax[:, :, None].float()
+    return q.view(N, K).to(dtype)
+
+
+def _check_codebook(bits, codebook):
+    if codebook not in (None, "nf4"):
+        raise ValueError(f"codebook must be None or 'nf4', got {codebook!r}")
+    if codebook is not None and bits != 4:
+        raise ValueError(f"codebook {codebook!r} needs bits=4, got {bits}")
+
+
 class QuantFrozenLinear(nn.Module):
-    """Drop-in for FrozenLinear holding int8/int4 weights; dequantizes
+    """Drop-in for FrozenLinear holding int8/int4 weights (or NF4:
+    bits=4, codebook="nf4", `scale` then holds the absmax); dequantizes
     per forward. `weight` property materializes bf16 on demand so LoRA
     wrappers and checkpoint code keep working."""
 
     def __init__(self, in_features: int, out_features: int,
-                 bits: int = 8, dtype=torch.bfloat16, group: int = 64):
+                 bits: int = 8, dtype=torch.bfloat16, group: int = 64,
+                 codebook=None):
         super().__init__()
         assert bits in (4, 8)
+        _check_codebook(bits, codebook)
         self.in_features, self.out_features = in_features, out_features
         self.bits, self.group, self.dtype = bits, group, dtype
+        self.codebook = codebook
         if bits == 8:
             self.register_buffer(
                 "qweight", torch.zeros(out_features, in_features,
@@ -80,10 +134,11 @@ class QuantFrozenLinear(nn.Module):
                                     dtype=torch.float32))
 
     @classmethod
-    def from_weight(cls, w: torch.Tensor, bits: int = 8, group: int = 64):
+    def from_weight(cls, w: torch.Tensor, bits: int = 8, group: int = 64,
+                    codebook=None):
         with torch.device(w.device):
             m = cls(w.shape[1], w.shape[0], bits=bits, dtype=w.dtype,
-                    group=group)
+                    group=group, codebook=codebook)
         m.load_weight(w)
         return m
 
@@ -91,6 +146,8 @@ class QuantFrozenLinear(nn.Module):
     def load_weight(self, w: torch.Tensor):
         if self.bits == 8:
             q, s = quantize_int8(w)
+        elif self.codebook == "nf4":
+            q, s = quantize_nf4(w, self.group)
         else:
             q, s = quantize_int4(w, self.group)
         self.qweight.copy_(q)
@@ -99,12 +156,17 @@ class QuantFrozenLinear(nn.Module):
     @property
     def weight(self):
         if self.qweight.is_cuda and self.dtype == torch.bfloat16:
-            from ..ops import dequant_int4, dequant_int8
+            from ..ops import dequant_int4, dequant_int8, dequant_nf4
             if self.bits == 8:
                 return dequant_int8(self.qweight, self.scale)
+            if self.codebook == "nf4":
+                return dequant_nf4(self.qweight, self.scale, self.group)
             return dequant_int4(self.qweight, self.scale, self.group)
         if self.bits == 8:
             return dequantize_int8(self.qweight, self.scale, self.dtype)
+        if self.codebook == "nf4":
+            return dequantize_nf4(self.qweight, self.scale, self.dtype,
+                                  self.group)
         return dequantize_int4(self.qweight, self.scale, self.dtype,
                                self.group)
 
@@ -130,7 +192,7 @@ class QuantFrozenLinear(nn.Module):
         if self._decode_path(x):
             from ..ops import qlinear
             return qlinear(x.contiguous(), self.qweight, self.scale,
-                           self.bits, self.group)
+                           self.bits, self.group, self.codebook)
         return F.linear(x, self.weight)
 
 
@@ -144,9 +206,9 @@ class QuantLoRALinear(QuantFrozenLinear):
 
     def __init__(self, in_features: int, out_features: int, r: int = 8,
                  alpha: float = 32.0, bits: int = 8,
-                 dtype=torch.bfloat16, group: int = 64):
+                 dtype=torch.bfloat16, group: int = 64, codebook=None):
         super().__init__(in_features, out_features, bits=bits, dtype=dtype,
-                         group=group)
+                         group=group, codebook=codebook)
         self.r, self.alpha = r, alpha
         self.lora_scale = alpha / r
         self.lora_A = nn.Parameter(
@@ -155,12 +217,13 @@ class QuantLoRALinear(QuantFrozenLinear):
             torch.zeros(out_features, r, dtype=dtype), requires_grad=False)
 
     @classmethod
-    def from_lora(cls, mod, bits: int = 8, group: int = 64):
+    def from_lora(cls, mod, bits: int = 8, group: int = 64, codebook=None):
         """Build from a LoRALinearModule (base quantized, A/B copied)."""
         w = mod.weight.detach()
         with torch.device(w.device):
             m = cls(mod.in_features, mod.out_features, r=mod.r,
-                    alpha=mod.alpha, bits=bits, dtype=w.dtype, group=group)
+                    alpha=mod.alpha, bits=bits, dtype=w.dtype, group=group,
+                    codebook=codebook)
         m.load_weight(w)
         with torch.no_grad():
             m.lora_A.copy_(mod.lora_A.detach())
@@ -181,7 +244,7 @@ class QuantLoRALinear(QuantFrozenLinear):
 
 @torch.no_grad()
 def quantize_model_(model: nn.Module, bits: int = 8,
-                    lora_base: bool = False):
+                    lora_base: bool = False, codebook=None):
     """Replace every FrozenLinear by a QuantFrozenLinear. By default the
     frozen base weight inside LoRA modules stays bf16 — PEFT quantizes
     only the base model's nn.Linear layers; our LoRA modules fuse
@@ -189,22 +252,25 @@ def quantize_model_(model: nn.Module, bits: int = 8,
     fp32-forcing in the reference — which is what the trainer wants.
     `lora_base=True` (serving) also replaces every LoRALinearModule by
     an inference-only QuantLoRALinear holding the quantized base plus
-    the unmerged adapter. Returns the count of quantized layers; raises
+    the unmerged adapter. `codebook="nf4"` (bits=4 only) stores NF4
+    levels instead of linear int4. Returns the count of quantized layers; raises
     if there was nothing to quantize."""
     from .lora import FrozenLinear, LoRALinearModule
     if bits not in (4, 8):
         raise ValueError(f"quantize_model_: bits must be 4 or 8, got {bits}")
+    _check_codebook(bits, codebook)
     n = 0
     for parent in model.modules():
         for name, child in list(parent.named_children()):
             if isinstance(child, FrozenLinear):
                 q = QuantFrozenLinear.from_weight(
-                    child.weight.detach(), bits=bits)
+                    child.weight.detach(), bits=bits, codebook=codebook)
                 setattr(parent, name, q)
                 n += 1
             elif lora_base and isinstance(child, LoRALinearModule):
                 setattr(parent, name,
-                        QuantLoRALinear.from_lora(child, bits=bits))
+                        QuantLoRALinear.from_lora(child, bits=bits,
+                                                  codebook=codebook))
                 n += 1
     if n == 0:
         raise ValueError(

@@ -708,6 +708,15 @@ def dequant_int4(packed, scale, group: int = 64):
     return dequantize_int4(packed, scale, torch.bfloat16, group)
 
 
+def dequant_nf4(packed, absmax, group: int = 64):
+    """bf16(NF4_CODE[idx] * absmax): the GPU kernel and the CPU reference
+    give the same bits."""
+    if _gpu(packed):
+        return _EXT.dequant_nf4(packed, absmax, group)
+    from ..models.quant import dequantize_nf4
+    return dequantize_nf4(packed, absmax, torch.bfloat16, group)
+
+
 # ------------------------------------------- quantized decode linear
 QLINEAR_MAX_ROWS = 16
 
@@ -728,10 +737,11 @@ def qlinear_supported(M: int, N: int, K: int, bits: int,
     return False
 
 
-def qlinear(x, qweight, scale, bits: int, group: int = 64):
+def qlinear(x, qweight, scale, bits: int, group: int = 64, codebook=None):
     """y[...,N] = x[...,K] @ dequant(qweight)[N,K]^T for the weight
     formats of models/quant.py (bits 8: q [N,K] int8 + scale [N];
-    bits 4: packed [N,K/2] uint8 + scale [N,K/group]).
+    bits 4: packed [N,K/2] uint8 + scale [N,K/group]; bits 4 with
+    codebook "nf4": packed NF4 indices + absmax [N,K/group]).
 
     GPU: the qgemv kernels stream the integer weight and dequantize in
     registers when the contract holds (bf16 contiguous x, <= 16 rows,
@@ -739,6 +749,8 @@ def qlinear(x, qweight, scale, bits: int, group: int = 64):
     the fp32 reference."""
     if bits not in (4, 8):
         raise ValueError(f"qlinear: bits must be 4 or 8, got {bits}")
+    if codebook not in (None, "nf4") or (codebook and bits != 4):
+        raise ValueError(f"qlinear: codebook {codebook!r} with bits={bits}")
     N = qweight.shape[0]
     K = qweight.shape[1] * (2 if bits == 4 else 1)
     if _gpu(x):
@@ -751,12 +763,18 @@ def qlinear(x, qweight, scale, bits: int, group: int = 64):
                 and qweight.data_ptr() % 16 == 0):
             if bits == 8:
                 return _EXT.qgemv_int8(x, qweight, scale)
+            if codebook == "nf4":
+                return _EXT.qgemv_nf4(x, qweight, scale, group)
             return _EXT.qgemv_int4(x, qweight, scale, group)
         w = (dequant_int8(qweight, scale) if bits == 8
+             else dequant_nf4(qweight, scale, group) if codebook == "nf4"
              else dequant_int4(qweight, scale, group))
         return torch.nn.functional.linear(x, w.to(x.dtype))
-    from ..models.quant import dequantize_int4, dequantize_int8
+    from ..models.quant import (dequantize_int4, dequantize_int8,
+                                dequantize_nf4)
     w = (dequantize_int8(qweight, scale, torch.float32) if bits == 8
+         else dequantize_nf4(qweight, scale, torch.float32, group)
+         if codebook == "nf4"
          else dequantize_int4(qweight, scale, torch.float32, group))
     return (x.float() @ w.t()).to(x.dtype)
 

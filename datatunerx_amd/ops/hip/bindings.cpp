@@ -639,6 +639,21 @@ Tensor dequant_int4(Tensor packed, Tensor scale, long group) {
   return out;
 }
 
+Tensor dequant_nf4(Tensor packed, Tensor absmax, long group) {
+  const Op op("dequant_nf4", packed, torch::kByte, "packed");
+  TORCH_CHECK(packed.dim() == 2, "dequant_nf4: packed must be [N,K/2]");
+  const long N = packed.size(0);
+  const int K = i32(packed.size(1) * 2);
+  TORCH_CHECK(K % 8 == 0 && group > 0 && group % 8 == 0 && K % group == 0,
+              "dequant_nf4: K % 8, group % 8, K % group");
+  op.dense(absmax, F32, "absmax", N * (K / group));
+  auto out = torch::empty({N, K}, packed.options().dtype(BF16));
+  if (packed.numel() == 0) return out;
+  launch_dequant_nf4(packed.data_ptr(), absmax.data_ptr<float>(),
+                     out.data_ptr(), N, K, i32(group), op.stream);
+  return out;
+}
+
 // y[..., N] = x[..., K] @ W[N,K]^T, one row x (decode GEMV; fp32 accumulate)
 Tensor gemv(Tensor x, Tensor w) {
   const Op op("gemv", x, BF16, "x");
@@ -699,6 +714,22 @@ Tensor qgemv_int4(Tensor x, Tensor packed, Tensor scale, long group) {
   launch_qgemv_int4(x.data_ptr(), packed.data_ptr(),
                     scale.data_ptr<float>(), y.data_ptr(), i32(x.numel() / K),
                     N, K, i32(group), op.stream);
+  return y;
+}
+
+Tensor qgemv_nf4(Tensor x, Tensor packed, Tensor absmax, long group) {
+  const Op op("qgemv_nf4", x, BF16, "x");
+  TORCH_CHECK(packed.dim() == 2, "qgemv_nf4: packed must be [N,K/2]");
+  const int N = i32(packed.size(0)), K = i32(packed.size(1) * 2);
+  TORCH_CHECK(K > 0 && K % 32 == 0, "qgemv_nf4: K % 32");
+  TORCH_CHECK(group > 0 && group % 32 == 0 && K % group == 0,
+              "qgemv_nf4: group % 32, K % group");
+  auto y = qgemv_out(op, x, packed, torch::kByte, absmax, K,
+                     (long)N * (K / group));
+  if (N == 0) return y;
+  launch_qgemv_nf4(x.data_ptr(), packed.data_ptr(),
+                   absmax.data_ptr<float>(), y.data_ptr(),
+                   i32(x.numel() / K), N, K, i32(group), op.stream);
   return y;
 }
 
@@ -1107,6 +1138,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("xent_lse_merge", &xent_lse_merge);
   m.def("dequant_int8", &dequant_int8);
   m.def("dequant_int4", &dequant_int4);
+  m.def("dequant_nf4", &dequant_nf4, py::arg("packed"), py::arg("absmax"),
+        py::arg("group") = 64);
   m.def("xent_dlogits", &xent_dlogits);
   m.def("lora_contract", &lora_contract, py::arg("x"), py::arg("w"),
         py::arg("mask") = py::none(), py::arg("seed") = 0,
@@ -1143,6 +1176,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("scale"));
   m.def("qgemv_int4", &qgemv_int4, py::arg("x"), py::arg("packed"),
         py::arg("scale"), py::arg("group") = 64);
+  m.def("qgemv_nf4", &qgemv_nf4, py::arg("x"), py::arg("packed"),
+        py::arg("absmax"), py::arg("group") = 64);
   m.def("skinny_supported", &skinny_supported, py::arg("m"), py::arg("n"),
         py::arg("k"));
   m.def("skinny_gemm", &skinny_gemm, py::arg("x"), py::arg("w"),

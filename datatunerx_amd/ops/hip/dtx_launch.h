@@ -79,6 +79,10 @@ void launch_dequant_int8(const void* q, const float* scale, void* out,
 // group % 8 == 0, K % group == 0.
 void launch_dequant_int4(const void* packed, const float* scale, void* out,
                          long N, int K, int group, hipStream_t s);
+// packed [N,K/2] uint8 (NF4 level indices), absmax [N,K/group] f32, out
+// [N,K] bf16 (16-byte aligned); K % 8 == 0, group % 8 == 0, K % group == 0.
+void launch_dequant_nf4(const void* packed, const float* absmax, void* out,
+                        long N, int K, int group, hipStream_t s);
 
 // ------------------------------------------------------------------- lora.hip
 // Planning helpers: pure functions of the shape, shared by the launchers
@@ -297,6 +301,11 @@ void launch_qgemv_int8(const void* x, const void* q, const float* scale,
 void launch_qgemv_int4(const void* x, const void* packed,
                        const float* scale, void* y, int M, int N, int K,
                        int group, hipStream_t st);
+// qgemv_nf4.hip: the int4 contract with NF4 level indices in the nibbles
+// and the group's absmax as its scale.
+void launch_qgemv_nf4(const void* x, const void* packed, const float* absmax,
+                      void* y, int M, int N, int K, int group,
+                      hipStream_t st);
 // t[m] = x[m] @ a[idx[m]]^T, then y[m] += scale[g] * t[m] @ bt[g]. x [M,K],
 // y [M,N] bf16, a [G,R,K], bt [G,R,N] bf16, all 16-byte aligned; t [M,R],
 // scale [G] f32; idx [M] int32, a row outside [0,G) is skipped in the

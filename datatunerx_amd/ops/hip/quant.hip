@@ -1,11 +1,13 @@
-// Weight-only dequantization kernels (gfx950): int8 per-row absmax and
-// int4 group-wise absmax -> bf16, one memory-bound pass (vectorized
+// Weight-only dequantization kernels (gfx950): int8 per-row absmax,
+// int4 group-wise absmax and NF4 (codebook index * group absmax) ->
+// bf16, one memory-bound pass (vectorized
 // int dword loads, bf16x8 stores). Replaces the eager-torch dequant
 // chain (fp32 materialize + cast) the round-1 quant path used on GPU
 // (VERDICT r1 weak #3). Reference exercise: bitsandbytes
 // BitsAndBytesConfig, /root/reference/cmd/tuning/train.py:224-234.
 #include "dtx_common.h"
 #include "dtx_launch.h"
+#include "dtx_nf4.h"
 
 // int8: q [N,K] int8 row-major, scale [N] f32 -> out [N,K] bf16.
 // Each thread handles 8 elements (two dwords of int8, one bf16x8 store).
@@ -56,6 +58,57 @@ void dequant_int4_kernel(const unsigned char* __restrict__ packed,
   }
 }
 
+// nf4: packed [N,K/2] (lo nibble = even k, nibble = level index), absmax
+// [N,K/g] f32 -> out [N,K] bf16 = bf16(level[idx] * absmax): one fp32
+// multiply, one rounding, so the result equals the CPU
+// dequantize_nf4(..., bfloat16) bit for bit. Thread = DW packed dwords =
+// 8*DW outputs inside one group: DW = 4 is one 16-byte load and four
+// 16-byte stores (K % 32 == 0, g % 32 == 0, packed 16-byte aligned),
+// DW = 1 takes the rest (K % 8 == 0, g % 8 == 0). The levels sit in LDS
+// as 256 fp32 pairs indexed by the whole weight byte: one ds_read_b64
+// gives both weights of a byte in k order.
+template <int DW>
+__global__ __launch_bounds__(DTX_BLOCK)
+void dequant_nf4_kernel(const unsigned char* __restrict__ packed,
+                        const float* __restrict__ absmax,
+                        unsigned short* __restrict__ out, long N, int K,
+                        int group) {
+  typedef __attribute__((ext_vector_type(2))) float f32x2;
+  typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
+  typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
+  __shared__ f32x2 tab[256];
+  for (int b = threadIdx.x; b < 256; b += DTX_BLOCK)
+    tab[b] = (f32x2){dtx_nf4_level(b & 15), dtx_nf4_level(b >> 4)};
+  __syncthreads();
+  const int per = K / (8 * DW);                  // threads per row
+  const long total = N * (long)per;
+  for (long i = (long)blockIdx.x * DTX_BLOCK + threadIdx.x; i < total;
+       i += (long)gridDim.x * DTX_BLOCK) {
+    const long row = i / per;
+    const int k0 = (int)(i % per) * (8 * DW);
+    const float s = absmax[row * (K / group) + k0 / group];
+    unsigned p[DW];
+    if (DW == 4) {
+      const u32x4 v = *reinterpret_cast<const u32x4*>(packed + i * 16);
+#pragma unroll
+      for (int d = 0; d < DW; ++d) p[d] = v[d];
+    } else {
+      p[0] = *reinterpret_cast<const unsigned*>(packed + i * 4);
+    }
+#pragma unroll
+    for (int d = 0; d < DW; ++d) {
+      u32x4 o;
+#pragma unroll
+      for (int b = 0; b < 4; ++b) {
+        const f32x2 w = tab[(p[d] >> (8 * b)) & 0xffu] * s;
+        o[b] = __builtin_bit_cast(unsigned,
+                                  __builtin_convertvector(w, bf16x2));
+      }
+      *reinterpret_cast<u32x4*>(out + i * (8 * DW) + 8 * d) = o;
+    }
+  }
+}
+
 void launch_dequant_int8(const void* q, const float* scale, void* out,
                          long N, int K, hipStream_t stream) {
   const long total = N * (long)(K / 8);
@@ -74,4 +127,21 @@ void launch_dequant_int4(const void* packed, const float* scale, void* out,
   hipLaunchKernelGGL(dequant_int4_kernel, dim3(blocks), dim3(DTX_BLOCK),
                      0, stream, (const unsigned char*)packed, scale,
                      (unsigned short*)out, N, K, group);
+}
+
+void launch_dequant_nf4(const void* packed, const float* absmax, void* out,
+                        long N, int K, int group, hipStream_t stream) {
+  const bool wide = K % 32 == 0 && group % 32 == 0 &&
+                    reinterpret_cast<uintptr_t>(packed) % 16 == 0;
+  const long total = N * (long)(K / (wide ? 32 : 8));
+  const int blocks = (int)min((total + DTX_BLOCK - 1) / DTX_BLOCK,
+                              (long)2048);
+  if (wide)
+    hipLaunchKernelGGL(dequant_nf4_kernel<4>, dim3(blocks), dim3(DTX_BLOCK),
+                       0, stream, (const unsigned char*)packed, absmax,
+                       (unsigned short*)out, N, K, group);
+  else
+    hipLaunchKernelGGL(dequant_nf4_kernel<1>, dim3(blocks), dim3(DTX_BLOCK),
+                       0, stream, (const unsigned char*)packed, absmax,
+                       (unsigned short*)out, N, K, group);
 }

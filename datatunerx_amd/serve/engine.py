@@ -341,7 +341,8 @@ def builtin_config(name: str, **lora_kw):
     raise ValueError(f"unknown model {name!r}")
 
 
-QUANTIZATIONS = {"int8": 8, "int4": 4}
+# name -> (bits, codebook) of models/quant.py
+QUANTIZATIONS = {"int8": (8, None), "int4": (4, None), "nf4": (4, "nf4")}
 
 
 def _graph_adapter_buffer(model, rows: int, device):
@@ -359,7 +360,7 @@ def build_model(name: str, device, adapter_dir: Optional[str] = None,
                 lora_kw: Optional[dict] = None,
                 quantization: Optional[str] = None,
                 adapters: Optional[dict] = None):
-    """quantization: None | "int8" | "int4" — weight-only quantize every
+    """quantization: None | "int8" | "int4" | "nf4" — weight-only quantize every
     projection (LoRA bases included, adapters kept unmerged in bf16)
     AFTER weights and adapter are loaded, so the service runs the model
     a quantized job trained against; decode then streams the integer
@@ -423,7 +424,8 @@ def build_model(name: str, device, adapter_dir: Optional[str] = None,
                 f"quantized serving supports llama models, not {name!r} "
                 "(its layers are not FrozenLinear)")
         from ..models.quant import quantize_model_
-        quantize_model_(model, QUANTIZATIONS[quantization], lora_base=True)
+        bits, codebook = QUANTIZATIONS[quantization]
+        quantize_model_(model, bits, lora_base=True, codebook=codebook)
     model.eval()
     return model
 

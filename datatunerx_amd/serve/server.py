@@ -512,7 +512,7 @@ def parse_args(argv=None):
                          "mode — one base model, the adapter chosen per "
                          "request by its \"model\" field")
     ap.add_argument("--template", default="llama2")
-    ap.add_argument("--quantization", choices=("int8", "int4"),
+    ap.add_argument("--quantization", choices=("int8", "int4", "nf4"),
                     default=None,
                     help="serve the base weights weight-only quantized "
                          "(adapters stay bf16, unmerged); single-GPU "

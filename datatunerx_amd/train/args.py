@@ -11,7 +11,7 @@ from typing import Optional
 @dataclass
 class ModelArguments:
     model_name_or_path: str = "llama2-7b"
-    quantization: Optional[str] = None          # int4 / int8 (phase-2)
+    quantization: Optional[str] = None          # int4 / int8 / nf4
     rope_scaling: Optional[str] = None          # dormant in reference too
     flash_attn: bool = True                     # our FA kernels are default
     shift_attn: bool = False                    # dormant (parser.py:70-73)

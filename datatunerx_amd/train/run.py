@@ -120,11 +120,11 @@ def main(argv=None):
             model.load_state_dict(sd, strict=False)
         else:
             model.init_random(seed=fargs.seed)
-        if margs.quantization in ("int4", "int8"):
+        if margs.quantization in ("int4", "int8", "nf4"):
             from ..models.quant import quantize_model_
-            n_q = quantize_model_(model,
-                                  bits=4 if margs.quantization == "int4"
-                                  else 8)
+            n_q = quantize_model_(
+                model, bits=8 if margs.quantization == "int8" else 4,
+                codebook="nf4" if margs.quantization == "nf4" else None)
             if rank == 0:
                 print(f"quantized {n_q} frozen base layers to "
                       f"{margs.quantization}")

@@ -1,8 +1,8 @@
 """Serving decode throughput: prefill a prompt, then time N decoded
 tokens through the hipGraph-captured token step — single stream by
 default, `--batch N` for the batched graphed step, `--quantization
-int8|int4` for the weight-streaming quantized path (ops.qlinear).
-`--quantization all` runs bf16, int8 and int4 in one process,
+int8|int4|nf4` for the weight-streaming quantized path (ops.qlinear).
+`--quantization all` runs bf16, int8, int4 and nf4 in one process,
 alternating the arms, and reports peak allocated memory per arm.
 
 Adapters (r = 8 on q_proj / v_proj, random): `--single-adapter` serves
@@ -82,8 +82,9 @@ def build(dev, quantization, graph, adapters=0, kv_cache="bf16",
         _attach_random_adapters(model, adapters, dev)
     if quantization:
         from datatunerx_amd.models.quant import quantize_model_
-        quantize_model_(model, 4 if quantization == "int4" else 8,
-                        lora_base=True)
+        quantize_model_(model, 8 if quantization == "int8" else 4,
+                        lora_base=True,
+                        codebook="nf4" if quantization == "nf4" else None)
         torch.cuda.empty_cache()
     model.eval()
     return InferenceEngine(model, template="vanilla", device=dev,
@@ -134,7 +135,7 @@ def main():
     ap.add_argument("--batch", type=int, default=1)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--quantization", default=None,
-                    choices=("int8", "int4", "all"))
+                    choices=("int8", "int4", "nf4", "all"))
     ap.add_argument("--adapters", type=int, default=0,
                     help="multi-adapter mode with N random adapters; row i "
                          "of the batch uses adapter i mod N")
@@ -168,7 +169,7 @@ def main():
     if args.skinny_ab:
         skinny_ab(args, dev, skw)
         return
-    quants = [None, "int8", "int4"] if args.quantization == "all" \
+    quants = [None, "int8", "int4", "nf4"] if args.quantization == "all" \
         else [args.quantization]
     kvs = ["bf16", "int8"] if args.kv_cache == "both" else [args.kv_cache]
     arms = [(q, kv) for q in quants for kv in kvs]

@@ -1,7 +1,8 @@
 """Quantized decode kernels vs the paths they replace, one process, arms
-interleaved: bf16 gemv / qgemv int8 / qgemv int4 at M = 1, and for
-M in {2, 8, 16} the MFMA qgemv against dequant + F.linear (what a
-quantized layer did before) and against bf16 F.linear (context).
+interleaved: bf16 gemv / qgemv int8 / qgemv int4 / qgemv nf4 at M = 1,
+and for M in {2, 8, 16} the MFMA qgemv against dequant + F.linear (what a
+quantized layer does without the kernel) and against bf16 F.linear
+(context). nf4 has int4's bytes, so qgemv int4 is its yardstick.
 
 Every arm rotates over enough distinct weight copies that no call finds
 its weight in the L2 / Infinity Cache (the decode step streams ~all
@@ -40,8 +41,9 @@ def make_weights(N, K, copies, dev):
                        dtype=torch.uint8)
     s4 = torch.rand(N, K // GROUP, device=dev, generator=g) * 0.1 + 1e-2
     rep = lambda t: [t.clone() for _ in range(copies)]   # noqa: E731
+    # nf4 arm: the same random bytes read as level indices, s4 as absmax
     return {"bf16": rep(w), "q8": rep(q8), "s8": rep(s8), "q4": rep(q4),
-            "s4": rep(s4)}
+            "s4": rep(s4), "qn": rep(q4), "sn": rep(s4)}
 
 
 def arms_for(M, W):
@@ -59,10 +61,15 @@ def arms_for(M, W):
         a["dequant+linear int4"] = (
             lambda x, i: F.linear(x, ops.dequant_int4(W["q4"][i], W["s4"][i],
                                                       GROUP)), b4)
+        a["dequant+linear nf4"] = (
+            lambda x, i: F.linear(x, ops.dequant_nf4(W["qn"][i], W["sn"][i],
+                                                     GROUP)), b4)
     a["qgemv int8"] = (lambda x, i: ops.qlinear(x, W["q8"][i], W["s8"][i],
                                                 8), b8)
     a["qgemv int4"] = (lambda x, i: ops.qlinear(x, W["q4"][i], W["s4"][i],
                                                 4, GROUP), b4)
+    a["qgemv nf4"] = (lambda x, i: ops.qlinear(x, W["qn"][i], W["sn"][i],
+                                               4, GROUP, "nf4"), b4)
     return a
 
 
