@@ -123,6 +123,7 @@ class FinetuneController:
             add("--packing", "true")          # sequence packing (sft | pt)
         add("--lr_scheduler_type", p.get("scheduler"))
         add("--optim", p.get("optimizer"))
+        add("--base_gemm", p.get("baseGemm"))  # bf16 | fp8 frozen GEMMs
         if p.get("nf4"):
             add("--quantization", "nf4")
         elif p.get("int4"):

@@ -152,7 +152,8 @@ class Hyperparameter(ApiObject):
     warmupRatio, weightDecay, gradAccSteps, trainerType, PEFT, FP16
     (finetune_controller.go:483-506); stage (sft | pt | dpo), dpoBeta,
     packing (bool: sequence packing of the training set, sft and pt
-    only)."""
+    only); baseGemm (bf16 | fp8: arithmetic of the frozen base GEMMs,
+    LoRA only)."""
     kind = "Hyperparameter"
     api_version = GROUP_CORE
 

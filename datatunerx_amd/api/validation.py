@@ -169,6 +169,12 @@ def validate_(obj: ApiObject) -> None:
             _require(not (pk is True and st == "dpo"),
                      "spec.parameters.packing is not supported with "
                      "stage dpo", errs)
+            bg = params.get("baseGemm")
+            _require(bg is None or bg in ("bf16", "fp8"),
+                     "spec.parameters.baseGemm must be bf16 or fp8", errs)
+            _require(not (bg == "fp8" and params.get("PEFT") is False),
+                     "spec.parameters.baseGemm fp8 needs frozen base "
+                     "weights (PEFT)", errs)
     elif isinstance(obj, Dataset):
         md = _dict(obj.spec.get("datasetMetadata"),
                    "spec.datasetMetadata", errs)

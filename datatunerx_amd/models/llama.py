@@ -21,7 +21,7 @@ from ..ops import (KV8, attn_decode_q8, doc_end_from_start, rope_tables,
 from ..ops.autograd import (PairedFrozenGemm, QKVProj, attention,
                             cross_entropy, rmsnorm, rmsnorm_tap,
                             rope, swiglu)
-from .lora import (FrozenLinear, LoRALinearModule, _weight_t,
+from .lora import (FrozenLinear, LoRALinearModule, _weight_t, fp8_operands,
                    draw_dropout_seed)
 from .multilora import MultiLoRALinear
 
@@ -185,11 +185,13 @@ class LlamaAttention(nn.Module):
                 keep = 1.0 - qm.dropout
                 sq = draw_dropout_seed()
                 sv = draw_dropout_seed()
+            f8 = fp8_operands((qm, km, vm), x)
+            wqt, wkt, wvt = (None if f8 else _weight_t(m)
+                             for m in (qm, km, vm))
             q, k, v = QKVProj.apply(x, qm.weight, qm.lora_A, qm.lora_B,
                                     km.weight, vm.weight, vm.lora_A,
                                     vm.lora_B, qm.scale, sq, sv, keep,
-                                    _weight_t(qm), _weight_t(km),
-                                    _weight_t(vm))
+                                    wqt, wkt, wvt, f8)
         else:
             q = _mproj(self.q_proj, x, adapters)
             k = _mproj(self.k_proj, x, adapters)
@@ -245,10 +247,12 @@ class LlamaMLP(nn.Module):
                 not self.gate_proj.weight.requires_grad:
             # one node for the gate/up pair: backward accumulates both
             # dgrads with addmm_ instead of a grad-add per layer
+            f8 = fp8_operands((self.gate_proj, self.up_proj), x)
+            wgt, wut = (None if f8 else _weight_t(m)
+                        for m in (self.gate_proj, self.up_proj))
             g, u = PairedFrozenGemm.apply(x, self.gate_proj.weight,
-                                          self.up_proj.weight,
-                                          _weight_t(self.gate_proj),
-                                          _weight_t(self.up_proj))
+                                          self.up_proj.weight, wgt, wut,
+                                          *(f8 or (None, None)))
             h = swiglu(g, u)
         else:
             h = swiglu(_mproj(self.gate_proj, x, adapters),

@@ -19,7 +19,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from ..ops import gemm_nt_supported, skinny_decode_rows, skinny_linear
+from ..ops import (SKINNY_MAX_ROWS, gemm_fp8_supported, gemm_nt_supported,
+                   quant_fp8_rows, skinny_decode_rows, skinny_linear)
 from ..ops.autograd import FrozenGemm
 from ..ops.autograd import LoRALinear as _FusedLoRAFn
 
@@ -83,14 +84,70 @@ def _weight_t(mod: nn.Module, any_device: bool = False):
         return None
     if not dgrad_wt_pays(*w.shape):
         return None
+    return _cached(mod, "_wt", lambda: w.detach().t().contiguous())
+
+
+def _cached(mod: nn.Module, slot: str, build):
+    """mod.__dict__[slot] = (key, build()), rebuilt when the weight's
+    data_ptr(), _version or count of `.data` uses changed."""
+    w = mod.weight
     if type(w) is nn.Parameter:
         w.__class__ = _DataTrackedParameter
     key = (w.data_ptr(), w._version, w.__dict__.get("_data_uses", 0))
-    cached = mod.__dict__.get("_wt")
+    cached = mod.__dict__.get(slot)
     if cached is None or cached[0] != key:
-        cached = (key, w.detach().t().contiguous())
-        mod.__dict__["_wt"] = cached
+        cached = (key, build())
+        mod.__dict__[slot] = cached
     return cached[1]
+
+
+BASE_GEMM_MODES = ("bf16", "fp8")
+FP8_MAX_FEATURES = 16384     # quant_fp8_rows holds a row in registers
+
+
+def set_base_gemm(model: nn.Module, mode: str) -> None:
+    """Choose how the frozen base projections of `model` multiply: "bf16"
+    (default) or "fp8" (ops/hip/gemm_fp8.hip). The lm_head keeps bf16:
+    logits are not computed in fp8."""
+    if mode not in BASE_GEMM_MODES:
+        raise ValueError(f"base_gemm must be one of {BASE_GEMM_MODES}, "
+                         f"got {mode!r}")
+    for name, mod in model.named_modules():
+        if isinstance(mod, (FrozenLinear, LoRALinearModule)):
+            head = "lm_head" in name.split(".")
+            mod.base_gemm = "bf16" if head else mode
+
+
+def _weight_fp8(mod: nn.Module, x):
+    """The fp8 route of one module for the activation x, or None: the
+    cached (w8, sw, wt8, swt) = quant_fp8_rows(W), quant_fp8_rows(W^T) of
+    its frozen weight. THE routing predicate of the fp8 base GEMMs: mode
+    fp8 on this module (set_base_gemm; never the lm_head), a frozen bf16
+    weight, more than 16 activation rows (the decode kernels keep theirs),
+    both dimensions within the quantizer's row limit and, on the GPU,
+    [N,K] and [K,N] inside the kernel's support. The cache lives beside
+    _wt under the same rules (keyed like it, no parameter, no buffer,
+    dropped by __getstate__); a routed module builds no bf16 W^T."""
+    w = mod.weight
+    n, k = w.shape
+    if (getattr(mod, "base_gemm", "bf16") != "fp8" or w.requires_grad
+            or w.dtype != torch.bfloat16 or x.dtype != torch.bfloat16
+            or x.numel() // x.shape[-1] <= SKINNY_MAX_ROWS
+            or max(n, k) > FP8_MAX_FEATURES or n % 8 or k % 8):
+        return None
+    if w.is_cuda and not (gemm_fp8_supported(n, k)
+                          and gemm_fp8_supported(k, n)):
+        return None
+    return _cached(mod, "_w8", lambda: (
+        *quant_fp8_rows(w.detach()),
+        *quant_fp8_rows(w.detach().t().contiguous())))
+
+
+def base_operands(mod: nn.Module, x):
+    """(wt, f8) for the autograd nodes: the fp8 operands when the module
+    routes there (and then no W^T), else the cached bf16 W^T or None."""
+    f8 = _weight_fp8(mod, x)
+    return (None, f8) if f8 is not None else (_weight_t(mod), None)
 
 
 def _state_without_wt(self):
@@ -99,7 +156,16 @@ def _state_without_wt(self):
     copy rebuilds its own on first use)."""
     state = self.__dict__.copy()
     state.pop("_wt", None)
+    state.pop("_w8", None)
     return state
+
+
+def fp8_operands(mods, x):
+    """The fp8 operands of the modules that share x inside ONE autograd
+    node (q/k/v, gate/up), or None: the node takes the fp8 route for all
+    of them or for none."""
+    f8 = tuple(_weight_fp8(m, x) for m in mods)
+    return None if None in f8 else f8
 
 
 def _custom_gemm(w, wt) -> bool:
@@ -143,9 +209,9 @@ class FrozenLinear(nn.Module):
         if not self.weight.requires_grad:
             # one node: residual add in the GEMM epilogue without a copy
             # of the residual, dgrad against the cached W^T
-            wt = _weight_t(self)
+            wt, f8 = base_operands(self, x)
             return FrozenGemm.apply(x, self.weight, wt, residual,
-                                    _custom_gemm(self.weight, wt))
+                                    _custom_gemm(self.weight, wt), f8)
         # trainable base (full-parameter training): torch's own nodes
         if residual is not None:
             # fold the residual add into the GEMM epilogue (addmm,
@@ -189,13 +255,13 @@ class LoRALinearModule(nn.Module):
         nn.init.kaiming_uniform_(self.lora_A, a=math.sqrt(5))
 
     def forward(self, x):
-        wt = _weight_t(self)
+        wt, f8 = base_operands(self, x)
         seed, keep = 0, 1.0
         if self.training and self.dropout > 0.0:
             seed, keep = draw_dropout_seed(), 1.0 - self.dropout
         return _FusedLoRAFn.apply(x, self.weight, self.lora_A, self.lora_B,
                                   self.scale, wt, seed, keep,
-                                  _custom_gemm(self.weight, wt))
+                                  _custom_gemm(self.weight, wt), f8)
 
     def merged_weight(self):
         """W + s·B@A — used by the serving engine (no adapter overhead)."""

@@ -427,6 +427,35 @@ def gemm_nt_add(a, b, c):
     return torch.addmm(c, a, b.t())
 
 
+# ------------------------------------------------------- fp8 base GEMMs
+def gemm_fp8_supported(n: int, k: int) -> bool:
+    """[N,K] weights the e4m3 MFMA GEMM takes (gemm_fp8.hip): the
+    extension's own predicate, the one its binding checks."""
+    ext = _load_ext()
+    if ext is None:
+        raise RuntimeError("gemm_fp8_supported needs the HIP extension "
+                           f"(_dtx_hip): {_EXT_ERR}")
+    return bool(ext.gemm_fp8_supported(n, k))
+
+
+def quant_fp8_rows(x):
+    """bf16 x [..., K] -> (q e4m3, scale f32 [rows]), one scale per row:
+    scale = absmax / 448, q = e4m3(clamp(x / scale)). The GPU kernel and
+    the CPU twin give the same bits."""
+    if _gpu(x):
+        return tuple(_EXT.quant_fp8_rows(x))
+    return ref.quant_fp8_rows(x)
+
+
+def gemm_fp8_nt(a8, sa, b8, sb, src=None):
+    """bf16 C[...,N] = sa[m] * sb[n] * (a8[...,K] @ b8[N,K]^T) (+ src) on
+    the 128-deep e4m3 MFMA (gemm_fp8.hip): fp32 accumulate, scales and src
+    in the fp32 epilogue, one rounding."""
+    if _gpu(a8):
+        return _EXT.gemm_fp8_nt(a8, sa, b8, sb, src)
+    return ref.gemm_fp8_nt(a8, sa, b8, sb, src)
+
+
 # --------------------------------------------- skinny bf16 decode GEMMs
 SKINNY_MAX_ROWS = 16
 

@@ -10,9 +10,10 @@ import os
 
 import torch
 
-from . import (attn_bwd, attn_fwd, gemm_nt_add, lora_contract,
+from . import (attn_bwd, attn_fwd, gemm_fp8_nt, gemm_nt_add, lora_contract,
                lora_contract2, lora_expand_add2, lora_expand_add_t,
-               lora_wgrad, rmsnorm_bwd, rmsnorm_fwd, rope_bwd, rope_fwd,
+               lora_wgrad, quant_fp8_rows, rmsnorm_bwd, rmsnorm_fwd, rope_bwd,
+               rope_fwd,
                skinny_decode_rows, skinny_linear, skinny_linear_multi,
                softmax_xent_bwd, softmax_xent_fwd, swiglu_bwd, swiglu_fwd)
 
@@ -184,20 +185,34 @@ def per_row_cross_entropy(logits, targets, ignore_index: int = -100):
     return PerRowCrossEntropy.apply(logits, targets, ignore_index)
 
 
-def _base_gemm(x2, w, custom):
-    """Base-projection GEMM x2 @ W^T: the library's forward layout, or
-    the hand-written MFMA kernel (gemm.hip) when `custom` (opt-in)."""
+def _quant(t2, f8):
+    """The fp8 operand (q, scale) of an activation or gradient [M,K], once
+    per node, when the node's weights route to fp8 (`f8`); else None."""
+    return quant_fp8_rows(t2.contiguous()) if f8 is not None else None
+
+
+def _base_gemm(x2, w, custom, f8=None, xq=None, src=None):
+    """Base-projection GEMM x2 @ W^T (+ src): the library's forward
+    layout, the hand-written MFMA kernel (gemm.hip) when `custom`
+    (opt-in), or with f8 = (w8, sw, wt8, swt) and xq = _quant(x2) the
+    e4m3 kernel (gemm_fp8.hip), src in its epilogue."""
     from . import gemm_nt
+    if f8 is not None:
+        return gemm_fp8_nt(xq[0], xq[1], f8[0], f8[1], src)
+    assert src is None
     if custom and x2.is_cuda and x2.shape[0] > 0:
         return gemm_nt(x2, w)
     return torch.nn.functional.linear(x2, w)
 
 
-def _base_dgrad(dy2, w, wt, custom):
+def _base_dgrad(dy2, w, wt, custom, f8=None, dq=None):
     """dx = dy2 @ W of a frozen W [N,K]. With the cached wt = W^T [K,N]
     it is F.linear(dy2, wt): the same forward-layout GEMM as the forward
     pass (both operands contraction-contiguous) instead of the library's
-    slower "NN" form. `custom`: the hand-written NT kernel on wt."""
+    slower "NN" form. `custom`: the hand-written NT kernel on wt. f8, dq =
+    _quant(dy2): the e4m3 kernel on the quantized W^T."""
+    if f8 is not None:
+        return gemm_fp8_nt(dq[0], dq[1], f8[2], f8[3])
     if custom and wt is not None and dy2.is_cuda:
         from . import gemm_nt
         return gemm_nt(dy2, wt)
@@ -206,10 +221,12 @@ def _base_dgrad(dy2, w, wt, custom):
     return dy2 @ w
 
 
-def _dgrad_acc(dx, dy2, w, wt):
-    """dx += dy2 @ W in the GEMM epilogue (beta = 1), against the cached
-    W^T when there is one."""
-    dx.addmm_(dy2, w if wt is None else wt.t())
+def _dgrad_acc(dx, dy2, w, wt, f8=None, dq=None):
+    """dx + dy2 @ W in the GEMM epilogue (beta = 1; in place on the bf16
+    routes), against the cached W^T when there is one. Returns the sum."""
+    if f8 is not None:
+        return gemm_fp8_nt(dq[0], dq[1], f8[2], f8[3], dx)
+    return dx.addmm_(dy2, w if wt is None else wt.t())
 
 
 class LoRALinear(torch.autograd.Function):
@@ -218,7 +235,9 @@ class LoRALinear(torch.autograd.Function):
     W: [N,K] (frozen base, no wgrad). `wt` = the cached W^T (or None):
     the dgrad dx = dy @ W then runs in the forward layout, see
     _base_dgrad; `custom` routes both base GEMMs through the hand-written
-    gfx950 MFMA kernel (ops/hip/gemm.hip) instead of the library. When x
+    gfx950 MFMA kernel (ops/hip/gemm.hip) instead of the library; `f8` =
+    the weight's cached fp8 operands routes them through the e4m3 kernel
+    (_base_gemm), the low-rank kernels still read the bf16 x and dy. When x
     needs no gradient (layer 0 behind a frozen embedding) the base dgrad
     and the dx expand-add are skipped. The
     low-rank path is the fused HIP contract/expand pair. A: [r,K],
@@ -236,10 +255,12 @@ class LoRALinear(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w, a, b, scale, wt=None, seed=0, keep=1.0,
-                custom=False):
+                custom=False, f8=None):
         xs = x.shape
         x2 = x.reshape(-1, xs[-1])
-        if x2.is_cuda and x2.shape[0] == 1 and keep >= 1.0:
+        if f8 is not None:
+            y = _base_gemm(x2, w, custom, f8, _quant(x2, f8))
+        elif x2.is_cuda and x2.shape[0] == 1 and keep >= 1.0:
             from . import gemv
             y = gemv(x2, w)                      # decode: streaming GEMV
         elif keep >= 1.0 and skinny_decode_rows(
@@ -251,25 +272,25 @@ class LoRALinear(torch.autograd.Function):
         t = lora_contract(x2, a, None, seed, keep)   # (x o mask) @ A^T
         lora_expand_add_t(y, t, bt, scale)       # y += s * t @ B^T
         ctx.save_for_backward(x2, w, a, bt, t, wt)
-        ctx.meta = (scale, seed, keep, xs, b.dtype, custom)
+        ctx.meta = (scale, seed, keep, xs, b.dtype, custom, f8)
         return y.reshape(*xs[:-1], w.shape[0])
 
     @staticmethod
     def backward(ctx, dy):
         x2, w, a, bt, t, wt = ctx.saved_tensors
-        s, seed, keep, xs, b_dtype, custom = ctx.meta
+        s, seed, keep, xs, b_dtype, custom, f8 = ctx.meta
         dy2 = dy.reshape(-1, dy.shape[-1]).contiguous()
         dt = lora_contract(dy2, bt)                   # [M,r] = dy @ B
         db = lora_wgrad(t, dy2, s).t().contiguous()   # [r,N] -> B is [N,r]
         da = lora_wgrad(dt, x2, s, None, seed, keep)  # dt^T @ (x o mask)
         dx = None
         if ctx.needs_input_grad[0]:
-            dx = _base_dgrad(dy2, w, wt, custom)
+            dx = _base_dgrad(dy2, w, wt, custom, f8, _quant(dy2, f8))
             # dx += mask o (s * dt @ A)
             lora_expand_add_t(dx, dt, a, s, None, seed, keep)
             dx = dx.reshape(xs)
         return (dx, None, da.to(a.dtype), db.to(b_dtype),
-                None, None, None, None, None)
+                None, None, None, None, None, None)
 
 
 def lora_linear(x, w, a, b, scale: float, wt=None):
@@ -285,15 +306,18 @@ class FrozenGemm(torch.autograd.Function):
     torch.addmm's copy of it into the result. Backward: dx = dy @ W
     against the cached `wt` = W^T when one is given (_base_dgrad); the
     residual's gradient is dy itself. `custom` runs both GEMMs on the
-    hand-written MFMA NT kernel instead (needs wt)."""
+    hand-written MFMA NT kernel instead (needs wt); `f8` runs both, and
+    the residual add, on the e4m3 kernel (_base_gemm)."""
 
     @staticmethod
-    def forward(ctx, x, w, wt, residual, custom=False):
+    def forward(ctx, x, w, wt, residual, custom=False, f8=None):
         xs = x.shape
         x2 = x.reshape(-1, xs[-1])
         r2 = residual.reshape(-1, w.shape[0]).contiguous() \
             if residual is not None else None
-        if custom:
+        if f8 is not None:
+            y = _base_gemm(x2, w, custom, f8, _quant(x2, f8), r2)
+        elif custom:
             from . import gemm_nt
             y = gemm_nt(x2, w, r2)
         elif r2 is not None and skinny_decode_rows(
@@ -308,6 +332,7 @@ class FrozenGemm(torch.autograd.Function):
             y = gemm_nt_add(x2.contiguous(), w, r2)
         ctx.save_for_backward(w, wt)
         ctx.xshape, ctx.has_res, ctx.custom = xs, residual is not None, custom
+        ctx.f8 = f8
         return y.reshape(*xs[:-1], w.shape[0])
 
     @staticmethod
@@ -316,8 +341,9 @@ class FrozenGemm(torch.autograd.Function):
         dx = None
         if ctx.needs_input_grad[0]:
             dy2 = dy.reshape(-1, dy.shape[-1]).contiguous()
-            dx = _base_dgrad(dy2, w, wt, ctx.custom).reshape(ctx.xshape)
-        return dx, None, None, dy if ctx.has_res else None, None
+            dx = _base_dgrad(dy2, w, wt, ctx.custom, ctx.f8,
+                             _quant(dy2, ctx.f8)).reshape(ctx.xshape)
+        return dx, None, None, dy if ctx.has_res else None, None, None
 
 
 class FusedLinearCrossEntropy(torch.autograd.Function):
@@ -405,27 +431,31 @@ class PairedFrozenGemm(torch.autograd.Function):
     MLP gate/up pair): backward ACCUMULATES the two dgrads into one
     buffer with addmm_ (beta=1 GEMM epilogue), eliminating the autograd
     grad-add that a shared input otherwise costs per layer. wgt / wut:
-    the cached W^T of each weight or None (_base_dgrad)."""
+    the cached W^T of each weight or None (_base_dgrad); f8g / f8u: the
+    fp8 operands of both weights, or None for both (_base_gemm)."""
 
     @staticmethod
-    def forward(ctx, x, wg, wu, wgt=None, wut=None):
+    def forward(ctx, x, wg, wu, wgt=None, wut=None, f8g=None, f8u=None):
         xs = x.shape
         x2 = x.reshape(-1, xs[-1])
-        g = torch.nn.functional.linear(x2, wg)
-        u = torch.nn.functional.linear(x2, wu)
+        xq = _quant(x2, f8g)                     # once, shared by gate/up
+        g = _base_gemm(x2, wg, False, f8g, xq)
+        u = _base_gemm(x2, wu, False, f8u, xq)
         ctx.save_for_backward(wg, wu, wgt, wut)
-        ctx.xshape = xs
+        ctx.xshape, ctx.f8 = xs, (f8g, f8u)
         n = wg.shape[0]
         return (g.reshape(*xs[:-1], n), u.reshape(*xs[:-1], n))
 
     @staticmethod
     def backward(ctx, dg, du):
         wg, wu, wgt, wut = ctx.saved_tensors
+        f8g, f8u = ctx.f8
         dg2 = dg.reshape(-1, dg.shape[-1])
         du2 = du.reshape(-1, du.shape[-1])
-        dx = _base_dgrad(dg2, wg, wgt, False)
-        _dgrad_acc(dx, du2, wu, wut)    # accumulate in the GEMM epilogue
-        return dx.reshape(ctx.xshape), None, None, None, None
+        dx = _base_dgrad(dg2, wg, wgt, False, f8g, _quant(dg2, f8g))
+        # accumulate in the GEMM epilogue
+        dx = _dgrad_acc(dx, du2, wu, wut, f8u, _quant(du2, f8u))
+        return dx.reshape(ctx.xshape), None, None, None, None, None, None
 
 
 class QKVProj(torch.autograd.Function):
@@ -442,14 +472,21 @@ class QKVProj(torch.autograd.Function):
     lora_A gradients stay two wgrad calls — a one-pass dual wgrad
     measured slower (profiles/README.md). lora_B is transposed once in
     the forward and the copy reused by the backward; lora_A is read in
-    its native [r,K] layout."""
+    its native [r,K] layout. `f8`: the fp8 operands of (wq, wk, wv), all
+    three or None (_base_gemm)."""
 
     @staticmethod
     def forward(ctx, x, wq, aq, bq, wk, wv, av, bv, scale,
-                seed_q, seed_v, keep, wqt=None, wkt=None, wvt=None):
+                seed_q, seed_v, keep, wqt=None, wkt=None, wvt=None,
+                f8=None):
         xs = x.shape
         x2 = x.reshape(-1, xs[-1])
-        if skinny_decode_rows(x2, 1, not any(ctx.needs_input_grad)):
+        if f8 is not None:
+            xq = _quant(x2, f8)                  # once, shared by q/k/v
+            yq = _base_gemm(x2, wq, False, f8[0], xq)
+            yk = _base_gemm(x2, wk, False, f8[1], xq)
+            yv = _base_gemm(x2, wv, False, f8[2], xq)
+        elif skinny_decode_rows(x2, 1, not any(ctx.needs_input_grad)):
             # decode: the three base GEMMs in one grouped launch
             yq, yk, yv = skinny_linear_multi(x2, [wq, wk, wv])
         else:
@@ -464,6 +501,7 @@ class QKVProj(torch.autograd.Function):
         ctx.save_for_backward(x2, wq, aq, bqt, wk, wv, av, bvt, tq, tv,
                               wqt, wkt, wvt)
         ctx.meta = (scale, seed_q, seed_v, keep, xs, bq.dtype, bv.dtype)
+        ctx.f8 = f8 if f8 is not None else (None, None, None)
         return (yq.reshape(*xs[:-1], wq.shape[0]),
                 yk.reshape(*xs[:-1], wk.shape[0]),
                 yv.reshape(*xs[:-1], wv.shape[0]))
@@ -487,13 +525,15 @@ class QKVProj(torch.autograd.Function):
             # x needs no gradient behind a frozen embedding (layer 0):
             # then the three base dgrads and the dx expand-add are not run
             dk2 = dyk.reshape(-1, dyk.shape[-1]).contiguous()
-            dx = _base_dgrad(dq2, wq, wqt, False)
-            _dgrad_acc(dx, dk2, wk, wkt)
-            _dgrad_acc(dx, dv2, wv, wvt)
+            f8q, f8k, f8v = ctx.f8
+            dx = _base_dgrad(dq2, wq, wqt, False, f8q, _quant(dq2, f8q))
+            dx = _dgrad_acc(dx, dk2, wk, wkt, f8k, _quant(dk2, f8k))
+            dx = _dgrad_acc(dx, dv2, wv, wvt, f8v, _quant(dv2, f8v))
             # low-rank dx terms (expand_add is in-place on dx)
             lora_expand_add2(dx, dtq, dtv, aq, av, scale, seed_q, seed_v,
                              keep)
             dx = dx.reshape(xs)
         return (dx, None, daq.to(aq.dtype),
                 dbq.to(bq_dtype), None, None, dav.to(av.dtype),
-                dbv.to(bv_dtype), None, None, None, None, None, None, None)
+                dbv.to(bv_dtype), None, None, None, None, None, None, None,
+                None)

@@ -18,6 +18,7 @@ constexpr auto BF16 = torch::kBFloat16;
 constexpr auto F32 = torch::kFloat;
 constexpr auto I32 = torch::kInt;
 constexpr auto I64 = torch::kLong;
+constexpr auto F8 = at::kFloat8_e4m3fn;
 
 // A size on its way to an int parameter of a launcher.
 static int i32(long v) {
@@ -32,6 +33,7 @@ const char* dt_name(at::ScalarType ty) {
     case at::kInt: return "int32";
     case at::kLong: return "int64";
     case at::kChar: return "int8";
+    case at::kFloat8_e4m3fn: return "float8_e4m3fn";
     default: return c10::toString(ty);
   }
 }
@@ -559,6 +561,51 @@ Tensor gemm_nt(Tensor a, Tensor b, OptTensor src) {
   if (M == 0 || N == 0) return c;
   launch_gemm_nt(a.data_ptr(), b.data_ptr(), sp, c.data_ptr(), M, N, K,
                  op.stream);
+  return c;
+}
+
+// x [..., K] bf16 -> (q [..., K] e4m3, scale [rows] f32), one scale per row
+// (gemm_fp8.hip). K % 8 == 0 and K <= quant_fp8_max_k(): the kernel holds a
+// row in registers.
+std::vector<Tensor> quant_fp8_rows(Tensor x) {
+  const Op op("quant_fp8_rows", x, BF16, "x");
+  const long M = op.rows(x, "x");
+  const long K = x.size(-1);
+  TORCH_CHECK(K % 8 == 0 && K <= quant_fp8_max_k(),
+              "quant_fp8_rows: x must have K % 8 == 0 and K <= ",
+              quant_fp8_max_k(), ", got K=", K);
+  op.aligned16("x", {x.data_ptr()});
+  auto q = torch::empty(x.sizes(), x.options().dtype(F8));
+  auto scale = torch::empty({M}, x.options().dtype(F32));
+  if (M > 0)
+    launch_quant_fp8_rows(x.data_ptr(), q.data_ptr(),
+                          scale.data_ptr<float>(), M, (int)K, op.stream);
+  return {q, scale};
+}
+
+// C[..., N] bf16 = sa[m] * sb[n] * (a8 [..., K] @ b8 [N,K]^T) (+ src), the
+// e4m3 MFMA GEMM of gemm_fp8.hip. gemm_fp8_supported(N, K); any M.
+Tensor gemm_fp8_nt(Tensor a8, Tensor sa, Tensor b8, Tensor sb,
+                   OptTensor src) {
+  const Op op("gemm_fp8_nt", a8, F8, "a8");
+  TORCH_CHECK(op.dense(b8, F8, "b8").dim() == 2,
+              "gemm_fp8_nt: b8 must be [N,K]");
+  const long N = b8.size(0), K = b8.size(1);
+  TORCH_CHECK(gemm_fp8_supported(N, K), "gemm_fp8_nt: b8 [N,K] must have "
+              "N % 256 == 0, K % 128 == 0 and K >= 256, got N=", N, " K=", K);
+  const long M = op.rows(a8, "a8", K);
+  op.dense(sa, F32, "sa", M);
+  op.dense(sb, F32, "sb", N);
+  const void* sp = op.opt(src, BF16, "src", M * N);
+  op.aligned16("a8, b8, sb, src",
+               {a8.data_ptr(), b8.data_ptr(), sb.data_ptr(), sp});
+  auto sizes = a8.sizes().vec();
+  sizes.back() = N;
+  auto c = torch::empty(sizes, a8.options().dtype(BF16));
+  if (M == 0) return c;
+  launch_gemm_fp8_nt(a8.data_ptr(), sa.data_ptr<float>(), b8.data_ptr(),
+                     sb.data_ptr<float>(), sp, c.data_ptr(), M, i32(N),
+                     i32(K), op.stream);
   return c;
 }
 
@@ -1194,6 +1241,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("sample_max_vocab", &sample_max_vocab);
   m.def("gemm_nt", &gemm_nt, py::arg("a"), py::arg("b"),
         py::arg("src") = py::none());
+  m.def("quant_fp8_rows", &quant_fp8_rows, py::arg("x"));
+  m.def("gemm_fp8_nt", &gemm_fp8_nt, py::arg("a8"), py::arg("sa"),
+        py::arg("b8"), py::arg("sb"), py::arg("src") = py::none());
+  m.def("gemm_fp8_supported", &gemm_fp8_supported, py::arg("n"),
+        py::arg("k"));
+  m.def("quant_fp8_max_k", &quant_fp8_max_k);
   m.def("gemm_nt_add", &gemm_nt_add, py::arg("a"), py::arg("b"),
         py::arg("c"));
   m.def("gemm_nt_add_workspace_bytes", &gemm_nt_add_workspace_bytes);

@@ -250,11 +250,27 @@ void launch_attn_bwd_dkdv(const void* q, const void* k, const void* v,
                           int S, int Skv, int D, float scale, int causal,
                           hipStream_t st);
 
-// ------------------------------------------------------- gemm.hip, gemv.hip
+// ------------------------------------------- gemm.hip, gemm_fp8.hip, gemv.hip
 // C[M,N] = A[M,K] @ B[N,K]^T (+ SRC [M,N] or nullptr), bf16.
 // N % 256 == 0, K % 64 == 0, K >= 128; any M >= 1.
 void launch_gemm_nt(const void* A, const void* B, const void* SRC, void* C,
                     long M, int N, int K, hipStream_t stream);
+// gemm_fp8.hip: x [M,K] bf16 -> q [M,K] e4m3 (one byte each), scale [M]
+// f32 with scale = absmax(row) / 448 (1 for a zero row) and q =
+// e4m3_rne(clamp(x / scale, -448, 448)). K % 8 == 0, 8 <= K <=
+// quant_fp8_max_k() (a row is held in registers); x, q 16-byte aligned.
+long quant_fp8_max_k();
+void launch_quant_fp8_rows(const void* x, void* q, float* scale, long M,
+                           int K, hipStream_t st);
+// Shapes the fp8 GEMM takes: N % 256 == 0, K % 128 == 0, 256 <= K <= 2^23.
+// The one predicate: the binding checks it and Python routes by it.
+bool gemm_fp8_supported(long N, long K);
+// C[M,N] bf16 = SA[m] * SB[n] * sum_k A[m,k] * B[n,k] (+ SRC [M,N] bf16 or
+// nullptr); A [M,K], B [N,K] e4m3, SA [M], SB [N] f32. All 16-byte aligned,
+// gemm_fp8_supported(N, K), any M >= 1.
+void launch_gemm_fp8_nt(const void* A, const float* SA, const void* B,
+                        const float* SB, const void* SRC, void* C, long M,
+                        int N, int K, hipStream_t stream);
 // basegemm.cpp, on hipBLASLt: D[M,N] = A[M,K] @ B[N,K]^T + C[M,N], bf16,
 // fp32 accumulate; C is only read, D != C. All four 16-byte aligned,
 // M, N, K >= 1. ws: ws_bytes of device scratch the call may use until it

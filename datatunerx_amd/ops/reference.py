@@ -572,3 +572,30 @@ def skinny_swiglu(x: torch.Tensor, wg: torch.Tensor, wu: torch.Tensor):
     """swiglu of the two projections, each rounded to x's dtype first as
     the two-GEMM path stores them."""
     return swiglu_fwd(skinny_linear(x, wg), skinny_linear(x, wu))
+
+
+# ------------------------------------------------------- fp8 base GEMMs
+FP8_MAX = 448.0     # largest finite OCP e4m3
+
+
+def quant_fp8_rows(x: torch.Tensor):
+    """bf16 x [..., K] -> (q e4m3 [..., K], scale f32 [rows]): scale =
+    absmax(row) / 448 in fp32 (1 for an all-zero row), q = e4m3_rne(
+    clamp(x / scale, -448, 448)). The clamp comes before the convert: a
+    rounded quotient can exceed 448."""
+    xf = x.float()
+    amax = xf.abs().amax(dim=-1, keepdim=True)
+    s = torch.where(amax > 0, amax / FP8_MAX, torch.ones_like(amax))
+    q = (xf / s).clamp(-FP8_MAX, FP8_MAX).to(torch.float8_e4m3fn)
+    return q, s.reshape(-1)
+
+
+def gemm_fp8_nt(a8: torch.Tensor, sa: torch.Tensor, b8: torch.Tensor,
+                sb: torch.Tensor, src=None):
+    """bf16(sa[m] * sb[n] * a8 [..., K] @ b8 [N,K]^T (+ src)): the fp32
+    product of the dequantized operands, any shape."""
+    a = a8.float() * sa.reshape(*a8.shape[:-1], 1)
+    out = a @ (b8.float() * sb[:, None]).t()
+    if src is not None:
+        out = out + src.float().reshape(out.shape)
+    return out.to(torch.bfloat16)

@@ -4,7 +4,8 @@ the operator's CR-field→flag mapping is finetune_controller.go:451-516)."""
 from __future__ import annotations
 
 import argparse
-from dataclasses import dataclass, field, fields
+import os
+from dataclasses import MISSING, dataclass, field, fields
 from typing import Optional
 
 
@@ -32,6 +33,10 @@ class FinetuningArguments:
     lora_alpha: float = 32.0
     lora_dropout: float = 0.1
     lora_target: str = "q_proj,v_proj"          # finetune_controller.go:482
+    base_gemm: str = field(                     # bf16 | fp8: frozen base
+        default_factory=lambda: os.environ.get("DTX_BASE_GEMM", "bf16"))
+                                  # GEMMs on the e4m3 MFMA kernel (LoRA
+                                  # only; lm_head and adapters stay bf16)
     num_workers: int = 1
     storage_path: Optional[str] = None
     metrics_export_address: Optional[str] = None
@@ -90,6 +95,7 @@ class DataArguments:
 def _add_dataclass_args(parser: argparse.ArgumentParser, dc) -> None:
     for f in fields(dc):
         name = "--" + f.name
+        default = f.default_factory() if f.default is MISSING else f.default
         if f.type in ("bool", bool) or isinstance(f.default, bool):
             # metadata flag=True: the bare switch (no value) means true
             kw = (dict(nargs="?", const=True)
@@ -103,7 +109,7 @@ def _add_dataclass_args(parser: argparse.ArgumentParser, dc) -> None:
                 typ = int
             elif isinstance(f.default, float):
                 typ = float
-            parser.add_argument(name, type=typ, default=f.default)
+            parser.add_argument(name, type=typ, default=default)
 
 
 def get_train_args(argv=None):
@@ -117,6 +123,12 @@ def get_train_args(argv=None):
         return dc(**{k: v for k, v in vars(ns).items() if k in names})
     margs, fargs, dargs = (pick(ModelArguments), pick(FinetuningArguments),
                            pick(DataArguments))
+    if fargs.base_gemm not in ("bf16", "fp8"):
+        raise ValueError(f"--base_gemm must be bf16 or fp8, got "
+                         f"{fargs.base_gemm!r}")
+    if fargs.base_gemm == "fp8" and fargs.finetuning_type == "full":
+        raise ValueError("--base_gemm fp8 needs frozen base weights; it is "
+                         "not supported with --finetuning_type full")
     if fargs.packing and fargs.stage == "dpo":
         raise ValueError("--packing is not supported with --stage dpo "
                          "(preference pairs are not packed)")

@@ -214,7 +214,8 @@ def main(argv=None):
             metrics_export_address=fargs.metrics_export_address,
             uid=fargs.uid, lora_r=fargs.lora_rank,
             lora_alpha=fargs.lora_alpha, lora_dropout=fargs.lora_dropout,
-            lora_targets=fargs.lora_targets, base_model=name)
+            lora_targets=fargs.lora_targets, base_model=name,
+            base_gemm=fargs.base_gemm)
         if dpo:
             from .trainer import DPOTrainer
             trainer = DPOTrainer(model, ds, tcfg, eval_dataset=eval_ds,

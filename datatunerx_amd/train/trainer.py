@@ -22,7 +22,7 @@ import json
 import math
 import os
 import time
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 from typing import Optional
 
 import torch
@@ -30,7 +30,7 @@ import torch
 from .. import ops
 from ..data.dataset import (DEFAULT_CUTOFF_LEN, PackedDataset,
                             ShardedLoader, collate_packed)
-from ..models.lora import LoRALinearModule, save_adapter
+from ..models.lora import LoRALinearModule, save_adapter, set_base_gemm
 from ..parallel.ddp import GradSynchronizer, is_main, sync_scalar_mean
 
 
@@ -59,6 +59,9 @@ class TrainerConfig:
     # cutoff_len; attention is masked by document, RoPE restarts at each
     packing: bool = False
     cutoff_len: int = DEFAULT_CUTOFF_LEN
+    # frozen base GEMMs: bf16, or fp8 (row-scaled e4m3, ops/hip/gemm_fp8.hip)
+    base_gemm: str = field(
+        default_factory=lambda: os.environ.get("DTX_BASE_GEMM", "bf16"))
     metrics_export_address: Optional[str] = None
     uid: str = ""
     # checkpoint metadata (adapter_config.json)
@@ -339,6 +342,7 @@ class SFTTrainer:
         self.cfg = cfg
         self.rank, self.world = rank, world_size
         self.device = device or next(model.parameters()).device
+        set_base_gemm(model, cfg.base_gemm)
         collate_fn = None
         if cfg.packing:
             # the step count below follows the number of packed rows
