@@ -495,6 +495,10 @@ class FinetuneJobController:
                 # quantized (int8/int4), as the job trained against it;
                 # admission rejects it together with tensorParallel > 1
                 args += ["--quantization", str(serve_cfg["quantization"])]
+            if serve_cfg.get("baseGemm") not in (None, "bf16"):
+                # serveConfig.baseGemm: serve the base in the arithmetic
+                # of the Hyperparameter baseGemm the job trained with
+                args += ["--base-gemm", str(serve_cfg["baseGemm"])]
             if serve_cfg.get("speculative"):
                 # serveConfig.speculative: draft tokens per decode step
                 # (prompt lookup); admission rejects it together with

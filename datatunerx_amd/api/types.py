@@ -119,7 +119,8 @@ class Finetune(ApiObject):
 class FinetuneJob(ApiObject):
     """spec: fineTune{name, finetuneSpec}, scoringPluginConfig{name,
     parameters}, serveConfig{tensorParallel, template, quantization
-    (int8|int4|nf4, single-GPU serving only)}. status: state,
+    (int8|int4|nf4, single-GPU serving only), baseGemm (bf16|fp8, as the
+    Hyperparameter's; single-GPU, not with quantization)}. status: state,
     finetuneStatus, result{
     modelExportResult, image, serve, dashboard, score}, stats
     (finetunejob_controller.go:71-143)."""

@@ -101,6 +101,17 @@ def validate_(obj: ApiObject) -> None:
             _require(not (isinstance(tp, int) and tp > 1),
                      "spec.serveConfig.quantization is not supported "
                      "with tensorParallel > 1", errs)
+        bg = sc.get("baseGemm")
+        if bg is not None:
+            _require(isinstance(bg, str) and bg in ("bf16", "fp8"),
+                     "spec.serveConfig.baseGemm must be bf16 or fp8", errs)
+            _require(not (bg == "fp8" and quant is not None),
+                     "spec.serveConfig.baseGemm fp8 and "
+                     "spec.serveConfig.quantization are mutually exclusive",
+                     errs)
+            _require(not (bg == "fp8" and isinstance(tp, int) and tp > 1),
+                     "spec.serveConfig.baseGemm fp8 is not supported "
+                     "with tensorParallel > 1", errs)
         spec_k = sc.get("speculative")
         if spec_k is not None:
             _require(isinstance(spec_k, int) and

@@ -97,18 +97,39 @@ def dequantize_nf4(packed: torch.Tensor, absmax: torch.Tensor, dtype,
     return q.view(N, K).to(dtype)
 
 
+def quantize_fp8(w: torch.Tensor):
+    """Per-output-row e4m3 (ops.quant_fp8_rows, the quantizer of the fp8
+    base GEMMs). Returns (w8 [N,K] e4m3, sw [N] f32)."""
+    from ..ops import quant_fp8_rows
+    return quant_fp8_rows(w.to(torch.bfloat16).contiguous())
+
+
+def dequantize_fp8(w8: torch.Tensor, sw: torch.Tensor, dtype):
+    return (w8.float() * sw[:, None]).to(dtype)
+
+
+_CODEBOOK_BITS = {"nf4": 4, "e4m3": 8}
+
+
 def _check_codebook(bits, codebook):
-    if codebook not in (None, "nf4"):
-        raise ValueError(f"codebook must be None or 'nf4', got {codebook!r}")
-    if codebook is not None and bits != 4:
-        raise ValueError(f"codebook {codebook!r} needs bits=4, got {bits}")
+    if codebook is not None and codebook not in _CODEBOOK_BITS:
+        raise ValueError("codebook must be None, 'nf4' or 'e4m3', got "
+                         f"{codebook!r}")
+    if codebook is not None and bits != _CODEBOOK_BITS[codebook]:
+        raise ValueError(f"codebook {codebook!r} needs "
+                         f"bits={_CODEBOOK_BITS[codebook]}, got {bits}")
 
 
 class QuantFrozenLinear(nn.Module):
     """Drop-in for FrozenLinear holding int8/int4 weights (or NF4:
     bits=4, codebook="nf4", `scale` then holds the absmax); dequantizes
     per forward. `weight` property materializes bf16 on demand so LoRA
-    wrappers and checkpoint code keep working."""
+    wrappers and checkpoint code keep working.
+
+    bits=8, codebook="e4m3": `qweight` is the e4m3 weight and `scale` its
+    per-row scale (quant_fp8_rows), one byte per weight and no W^T. Every
+    forward without a gradient, decode and prefill alike, multiplies under
+    the fp8 contract (ops.qlinear); nothing is dequantized."""
 
     def __init__(self, in_features: int, out_features: int,
                  bits: int = 8, dtype=torch.bfloat16, group: int = 64,
@@ -121,8 +142,10 @@ class QuantFrozenLinear(nn.Module):
         self.codebook = codebook
         if bits == 8:
             self.register_buffer(
-                "qweight", torch.zeros(out_features, in_features,
-                                       dtype=torch.int8))
+                "qweight", torch.zeros(
+                    out_features, in_features,
+                    dtype=torch.float8_e4m3fn if codebook == "e4m3"
+                    else torch.int8))
             self.register_buffer(
                 "scale", torch.ones(out_features, dtype=torch.float32))
         else:
@@ -144,7 +167,9 @@ class QuantFrozenLinear(nn.Module):
 
     @torch.no_grad()
     def load_weight(self, w: torch.Tensor):
-        if self.bits == 8:
+        if self.codebook == "e4m3":
+            q, s = quantize_fp8(w)
+        elif self.bits == 8:
             q, s = quantize_int8(w)
         elif self.codebook == "nf4":
             q, s = quantize_nf4(w, self.group)
@@ -155,6 +180,8 @@ class QuantFrozenLinear(nn.Module):
 
     @property
     def weight(self):
+        if self.codebook == "e4m3":
+            return dequantize_fp8(self.qweight, self.scale, self.dtype)
         if self.qweight.is_cuda and self.dtype == torch.bfloat16:
             from ..ops import dequant_int4, dequant_int8, dequant_nf4
             if self.bits == 8:
@@ -189,6 +216,11 @@ class QuantFrozenLinear(nn.Module):
                                  self.bits, self.group)
 
     def forward(self, x):
+        if self.codebook == "e4m3" and x.shape[-1] == self.in_features \
+                and not (torch.is_grad_enabled() and x.requires_grad):
+            from ..ops import qlinear
+            return qlinear(x.contiguous(), self.qweight, self.scale, 8,
+                           codebook="e4m3")
         if self._decode_path(x):
             from ..ops import qlinear
             return qlinear(x.contiguous(), self.qweight, self.scale,
@@ -253,7 +285,9 @@ def quantize_model_(model: nn.Module, bits: int = 8,
     `lora_base=True` (serving) also replaces every LoRALinearModule by
     an inference-only QuantLoRALinear holding the quantized base plus
     the unmerged adapter. `codebook="nf4"` (bits=4 only) stores NF4
-    levels instead of linear int4. Returns the count of quantized layers; raises
+    levels instead of linear int4; `codebook="e4m3"` (bits=8 only) stores
+    the row-scaled fp8 weight of the fp8 base GEMMs and, as there, leaves
+    the lm_head in bf16. Returns the count of quantized layers; raises
     if there was nothing to quantize."""
     from .lora import FrozenLinear, LoRALinearModule
     if bits not in (4, 8):
@@ -262,6 +296,8 @@ def quantize_model_(model: nn.Module, bits: int = 8,
     n = 0
     for parent in model.modules():
         for name, child in list(parent.named_children()):
+            if codebook == "e4m3" and name == "lm_head":
+                continue
             if isinstance(child, FrozenLinear):
                 q = QuantFrozenLinear.from_weight(
                     child.weight.detach(), bits=bits, codebook=codebook)

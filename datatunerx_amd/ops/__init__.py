@@ -748,16 +748,28 @@ def dequant_nf4(packed, absmax, group: int = 64):
 
 # ------------------------------------------- quantized decode linear
 QLINEAR_MAX_ROWS = 16
+# CPU-side copy of quant_fp8_max_k(), read only where the extension is not
+# loaded; with it loaded every fp8 shape rule is the extension's predicate
+FP8_QUANT_MAX_K = 16384
 
 
 def qlinear_supported(M: int, N: int, K: int, bits: int,
-                      group: int = 64) -> bool:
+                      group: int = 64, codebook=None) -> bool:
     """Shapes the weight-streaming qgemv kernels take (qgemv.hip): at
     most 16 rows, and a K that splits into whole 16-byte weight pieces
-    (each int4 piece inside one scale group). Anything else goes through
+    (each int4 piece inside one scale group). codebook "e4m3"
+    (qgemv_fp8.hip): whole 128-deep k-steps and a row the in-kernel
+    quantizer holds, FP8_QUANT_MAX_K. Anything else goes through
     dequantize-then-linear."""
     if not (1 <= M <= QLINEAR_MAX_ROWS and N >= 1 and K >= 1):
         return False
+    if codebook == "e4m3":
+        if bits != 8:
+            return False
+        ext = _load_ext()
+        if ext is not None:       # the one predicate, the binding's own
+            return bool(ext.qgemv_fp8_supported(M, N, K))
+        return K % 128 == 0 and K <= FP8_QUANT_MAX_K
     if bits == 8:
         return K % 16 == 0
     if bits == 4:
@@ -766,11 +778,36 @@ def qlinear_supported(M: int, N: int, K: int, bits: int,
     return False
 
 
+def _qlinear_fp8(x, w8, sw):
+    """The fp8 contract on an e4m3 weight: quant_fp8_rows on x, fp32
+    accumulation, both scales in the fp32 epilogue, one rounding. GPU: up
+    to 16 rows the weight-streaming kernel (it quantizes x itself), more
+    rows the quantizer and the e4m3 MFMA GEMM; only a shape outside both
+    kernels dequantizes and multiplies. CPU: the reference twin."""
+    N, K = w8.shape
+    if not _gpu(x):
+        return ref.qlinear_fp8(x, w8, sw)
+    M = x.numel() // K if K else 0
+    dense = (x.dtype == torch.bfloat16 and x.shape[-1] == K
+             and x.is_contiguous() and w8.is_contiguous()
+             and sw.is_contiguous() and x.data_ptr() % 16 == 0
+             and w8.data_ptr() % 16 == 0)
+    if dense and _EXT.qgemv_fp8_supported(M, N, K):
+        return _EXT.qgemv_fp8(x, w8, sw)
+    if (dense and M > QLINEAR_MAX_ROWS and K <= _EXT.quant_fp8_max_k()
+            and _EXT.gemm_fp8_supported(N, K) and sw.data_ptr() % 16 == 0):
+        return gemm_fp8_nt(*quant_fp8_rows(x), w8, sw)
+    w = (w8.float() * sw[:, None]).to(torch.bfloat16)
+    return torch.nn.functional.linear(x, w.to(x.dtype))
+
+
 def qlinear(x, qweight, scale, bits: int, group: int = 64, codebook=None):
     """y[...,N] = x[...,K] @ dequant(qweight)[N,K]^T for the weight
     formats of models/quant.py (bits 8: q [N,K] int8 + scale [N];
     bits 4: packed [N,K/2] uint8 + scale [N,K/group]; bits 4 with
-    codebook "nf4": packed NF4 indices + absmax [N,K/group]).
+    codebook "nf4": packed NF4 indices + absmax [N,K/group]; bits 8 with
+    codebook "e4m3": q [N,K] e4m3 + scale [N], multiplied under the fp8
+    contract, see _qlinear_fp8).
 
     GPU: the qgemv kernels stream the integer weight and dequantize in
     registers when the contract holds (bf16 contiguous x, <= 16 rows,
@@ -778,8 +815,11 @@ def qlinear(x, qweight, scale, bits: int, group: int = 64, codebook=None):
     the fp32 reference."""
     if bits not in (4, 8):
         raise ValueError(f"qlinear: bits must be 4 or 8, got {bits}")
-    if codebook not in (None, "nf4") or (codebook and bits != 4):
+    if codebook not in (None, "nf4", "e4m3") or \
+            (codebook and bits != {"nf4": 4, "e4m3": 8}[codebook]):
         raise ValueError(f"qlinear: codebook {codebook!r} with bits={bits}")
+    if codebook == "e4m3":
+        return _qlinear_fp8(x, qweight, scale)
     N = qweight.shape[0]
     K = qweight.shape[1] * (2 if bits == 4 else 1)
     if _gpu(x):

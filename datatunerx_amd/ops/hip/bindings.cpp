@@ -780,6 +780,30 @@ Tensor qgemv_nf4(Tensor x, Tensor packed, Tensor absmax, long group) {
   return y;
 }
 
+// fp8 decode: y[..., N] = bf16(sa * sw * quant_fp8_rows(x) @ w8^T) for up
+// to 16 rows, the activation quantized inside the kernel (qgemv_fp8.hip).
+// Only allocation is the output: hipGraph-capturable. No rows: no launch.
+Tensor qgemv_fp8(Tensor x, Tensor w8, Tensor sw) {
+  const Op op("qgemv_fp8", x, BF16, "x");
+  TORCH_CHECK(op.dense(w8, F8, "w8").dim() == 2,
+              "qgemv_fp8: w8 must be [N,K]");
+  const long N = w8.size(0), K = w8.size(1);
+  const long M = K > 0 ? op.rows(x, "x", K) : -1;
+  TORCH_CHECK(M == 0 || qgemv_fp8_supported(M, N, K),
+              "qgemv_fp8: x [M,K], w8 [N,K] must have 1 <= M <= 16, N >= 1, "
+              "K % 128 == 0 and 128 <= K <= ", quant_fp8_max_k(), ", got M=",
+              M, " N=", N, " K=", K);
+  op.dense(sw, F32, "sw", N);
+  op.aligned16("x, w8", {x.data_ptr(), w8.data_ptr()});
+  auto sizes = x.sizes().vec();
+  sizes.back() = N;
+  auto y = torch::empty(sizes, x.options());
+  if (M == 0) return y;
+  launch_qgemv_fp8(x.data_ptr(), w8.data_ptr(), sw.data_ptr<float>(),
+                   y.data_ptr(), i32(M), i32(N), i32(K), op.stream);
+  return y;
+}
+
 // bf16 decode at 1..16 rows: y = x @ W^T streaming the checkpoint's [N,K]
 // weight (skinny.hip). The only allocations are the outputs:
 // hipGraph-capturable. Checks x [..., K] and one weight against
@@ -1225,6 +1249,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("scale"), py::arg("group") = 64);
   m.def("qgemv_nf4", &qgemv_nf4, py::arg("x"), py::arg("packed"),
         py::arg("absmax"), py::arg("group") = 64);
+  m.def("qgemv_fp8", &qgemv_fp8, py::arg("x"), py::arg("w8"),
+        py::arg("sw"));
+  m.def("qgemv_fp8_supported", &qgemv_fp8_supported, py::arg("m"),
+        py::arg("n"), py::arg("k"));
   m.def("skinny_supported", &skinny_supported, py::arg("m"), py::arg("n"),
         py::arg("k"));
   m.def("skinny_gemm", &skinny_gemm, py::arg("x"), py::arg("w"),

@@ -322,6 +322,17 @@ void launch_qgemv_int4(const void* x, const void* packed,
 void launch_qgemv_nf4(const void* x, const void* packed, const float* absmax,
                       void* y, int M, int N, int K, int group,
                       hipStream_t st);
+// qgemv_fp8.hip: shapes the e4m3 weight-streaming kernel takes: 1 <= M <=
+// 16, N >= 1, K % 128 == 0, 128 <= K <= quant_fp8_max_k(). The one
+// predicate: the binding checks it and Python routes by it.
+bool qgemv_fp8_supported(long M, long N, long K);
+// y[M,N] bf16 = sa[m] * sw[n] * sum_k x8[m,k] * w8[n,k] with (x8, sa) =
+// quant_fp8_rows(x) formed in the kernel; x [M,K] bf16, w8 [N,K] e4m3, both
+// 16-byte aligned, sw [N] f32. qgemv_fp8_supported(M, N, K). The grid and
+// an output's summation order depend on (N, K) alone: a row's bits do not
+// depend on M.
+void launch_qgemv_fp8(const void* x, const void* w8, const float* sw,
+                      void* y, int M, int N, int K, hipStream_t st);
 // t[m] = x[m] @ a[idx[m]]^T, then y[m] += scale[g] * t[m] @ bt[g]. x [M,K],
 // y [M,N] bf16, a [G,R,K], bt [G,R,N] bf16, all 16-byte aligned; t [M,R],
 // scale [G] f32; idx [M] int32, a row outside [0,G) is skipped in the

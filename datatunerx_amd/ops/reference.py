@@ -590,6 +590,15 @@ def quant_fp8_rows(x: torch.Tensor):
     return q, s.reshape(-1)
 
 
+def qlinear_fp8(x: torch.Tensor, w8: torch.Tensor, sw: torch.Tensor):
+    """The fp8 decode linear (qgemv_fp8.hip): quant_fp8_rows on x, the fp32
+    product of the fp8 values, both scales, one rounding to x's dtype."""
+    x8, sa = quant_fp8_rows(x)
+    out = x8.float() @ w8.float().t()
+    out = out * sa.reshape(*x.shape[:-1], 1) * sw
+    return out.to(x.dtype)
+
+
 def gemm_fp8_nt(a8: torch.Tensor, sa: torch.Tensor, b8: torch.Tensor,
                 sb: torch.Tensor, src=None):
     """bf16(sa[m] * sb[n] * a8 [..., K] @ b8 [N,K]^T (+ src)): the fp32

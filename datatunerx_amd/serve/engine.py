@@ -343,6 +343,8 @@ def builtin_config(name: str, **lora_kw):
 
 # name -> (bits, codebook) of models/quant.py
 QUANTIZATIONS = {"int8": (8, None), "int4": (4, None), "nf4": (4, "nf4")}
+# base_gemm -> the same; bf16 quantizes nothing
+BASE_GEMMS = {"bf16": None, "fp8": (8, "e4m3")}
 
 
 def _graph_adapter_buffer(model, rows: int, device):
@@ -359,8 +361,16 @@ def _graph_adapter_buffer(model, rows: int, device):
 def build_model(name: str, device, adapter_dir: Optional[str] = None,
                 lora_kw: Optional[dict] = None,
                 quantization: Optional[str] = None,
-                adapters: Optional[dict] = None):
-    """quantization: None | "int8" | "int4" | "nf4" — weight-only quantize every
+                adapters: Optional[dict] = None,
+                base_gemm: str = "bf16"):
+    """base_gemm: "bf16" | "fp8" — "fp8" stores every base projection
+    (LoRA bases included, adapters unmerged in bf16, lm_head bf16) as the
+    row-scaled e4m3 weight an adapter trained with --base_gemm fp8 saw,
+    one byte per weight, and runs prefill (ops.gemm_fp8_nt) and decode
+    (the weight-streaming qgemv_fp8 kernel) in that one arithmetic.
+    Mutually exclusive with quantization.
+
+    quantization: None | "int8" | "int4" | "nf4" — weight-only quantize every
     projection (LoRA bases included, adapters kept unmerged in bf16)
     AFTER weights and adapter are loaded, so the service runs the model
     a quantized job trained against; decode then streams the integer
@@ -380,6 +390,12 @@ def build_model(name: str, device, adapter_dir: Optional[str] = None,
         raise ValueError(
             f"unknown quantization {quantization!r} "
             f"(expected one of {sorted(QUANTIZATIONS)})")
+    if base_gemm not in BASE_GEMMS:
+        raise ValueError(f"unknown base_gemm {base_gemm!r} "
+                         f"(expected one of {list(BASE_GEMMS)})")
+    if base_gemm != "bf16" and quantization is not None:
+        raise ValueError("build_model: base_gemm and quantization are "
+                         "mutually exclusive")
     dtype = torch.bfloat16 if device.type == "cuda" else torch.float32
     lora_kw = dict(lora_kw or {})
     if adapter_dir and not lora_kw:
@@ -418,13 +434,14 @@ def build_model(name: str, device, adapter_dir: Optional[str] = None,
     if adapters is not None:
         from ..models.multilora import attach_adapters_
         attach_adapters_(model, adapters)
-    if quantization is not None:
+    if quantization is not None or base_gemm != "bf16":
         if not isinstance(model, LlamaForCausalLM):
             raise ValueError(
                 f"quantized serving supports llama models, not {name!r} "
                 "(its layers are not FrozenLinear)")
         from ..models.quant import quantize_model_
-        bits, codebook = QUANTIZATIONS[quantization]
+        bits, codebook = (QUANTIZATIONS[quantization] if quantization
+                          else BASE_GEMMS[base_gemm])
         quantize_model_(model, bits, lora_base=True, codebook=codebook)
     model.eval()
     return model

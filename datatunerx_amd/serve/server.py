@@ -517,6 +517,12 @@ def parse_args(argv=None):
                     help="serve the base weights weight-only quantized "
                          "(adapters stay bf16, unmerged); single-GPU "
                          "llama models only")
+    ap.add_argument("--base-gemm", choices=("bf16", "fp8"), default="bf16",
+                    help="fp8: store the base projections as row-scaled "
+                         "e4m3 and run prefill and decode in the arithmetic "
+                         "of training's --base_gemm fp8 (adapters stay "
+                         "bf16, unmerged); single-GPU llama models only, "
+                         "not together with --quantization")
     ap.add_argument("--kv-cache", choices=("bf16", "int8"), default="bf16",
                     help="KV cache format; int8 halves the cache and its "
                          "decode traffic (single-GPU llama models inside "
@@ -586,11 +592,17 @@ def _check_adapters(args, world: int):
 def _check_quantization(args, world: int):
     """--quantization is refused at start-up where it cannot be honoured
     rather than silently serving bf16."""
-    if not args.quantization:
+    fp8 = getattr(args, "base_gemm", "bf16") != "bf16"
+    if not args.quantization and not fp8:
         return
+    flag = "--quantization" if args.quantization else "--base-gemm fp8"
+    if args.quantization and fp8:
+        raise SystemExit("--base-gemm fp8 and --quantization are mutually "
+                         "exclusive: each stores the base weights its own "
+                         "way")
     if world > 1:
         raise SystemExit(
-            "--quantization is not supported with tensor-parallel serving "
+            f"{flag} is not supported with tensor-parallel serving "
             f"(WORLD_SIZE={world}); serve quantized models on one GPU")
     from .engine import builtin_config
     from ..models.hf_io import is_hf_model_dir
@@ -601,7 +613,7 @@ def _check_quantization(args, world: int):
             raise SystemExit(str(e))
         if family != "llama":
             raise SystemExit(
-                f"--quantization supports llama models, not {args.model!r}")
+                f"{flag} supports llama models, not {args.model!r}")
 
 
 def _check_kv_cache(args, world: int):
@@ -751,15 +763,17 @@ def main(argv=None):
         return
     from ..models.hf_io import load_tokenizer
     device = torch.device("cuda:0" if torch.cuda.is_available() else "cpu")
+    # base_gemm is passed only when it is not the default
+    bg = {} if args.base_gemm == "bf16" else {"base_gemm": args.base_gemm}
     if args.adapters:
         try:
             model = build_model(args.model, device, adapters=args.adapters,
-                                quantization=args.quantization)
+                                quantization=args.quantization, **bg)
         except (ValueError, OSError) as e:
             raise SystemExit(f"--adapter: {e}")
     else:
         model = build_model(args.model, device, adapter_dir=args.adapter,
-                            quantization=args.quantization)
+                            quantization=args.quantization, **bg)
     pool, batcher = build_fronts(model, load_tokenizer(args.model), args,
                                  device)
     httpd = ThreadingHTTPServer((args.host, args.port),

@@ -82,9 +82,10 @@ def build(dev, quantization, graph, adapters=0, kv_cache="bf16",
         _attach_random_adapters(model, adapters, dev)
     if quantization:
         from datatunerx_amd.models.quant import quantize_model_
-        quantize_model_(model, 8 if quantization == "int8" else 4,
+        quantize_model_(model, 8 if quantization in ("int8", "fp8") else 4,
                         lora_base=True,
-                        codebook="nf4" if quantization == "nf4" else None)
+                        codebook={"nf4": "nf4", "fp8": "e4m3"}.get(
+                            quantization))
         torch.cuda.empty_cache()
     model.eval()
     return InferenceEngine(model, template="vanilla", device=dev,
@@ -154,6 +155,15 @@ def main():
                     choices=("bf16", "int8", "both"),
                     help="KV cache format; both: the two formats over the "
                          "same weights, interleaved")
+    ap.add_argument("--base-gemm", default="bf16", choices=("bf16", "fp8"),
+                    help="fp8: add the e4m3 base as an arm beside bf16 and "
+                         "the chosen --quantization")
+    ap.add_argument("--prefill-len", type=int, default=0,
+                    help="also time a prompt of this many tokens plus one "
+                         "decoded token, per arm")
+    ap.add_argument("--perplexity", action="store_true",
+                    help="also print engine.perplexity of every arm over "
+                         "paragraphs of the repository's README")
     ap.add_argument("--prompt-len", type=int, default=96)
     ap.add_argument("--skinny-ab", action="store_true",
                     help="bf16 with DTX_SKINNY_GEMM=0 and =1 over the same "
@@ -171,6 +181,8 @@ def main():
         return
     quants = [None, "int8", "int4", "nf4"] if args.quantization == "all" \
         else [args.quantization]
+    if args.base_gemm == "fp8":            # the serve mode --base-gemm fp8
+        quants = ["fp8", None] + [q for q in quants if q]
     kvs = ["bf16", "int8"] if args.kv_cache == "both" else [args.kv_cache]
     arms = [(q, kv) for q in quants for kv in kvs]
     adapters = -1 if args.single_adapter else args.adapters
@@ -193,6 +205,31 @@ def main():
         for q in arms:                     # arms alternate per repetition
             rates[q].append(run(engines[q], args.tokens, args.batch, skw,
                                 args.prompt_len))
+    if args.prefill_len:
+        pre = {q: [] for q in arms}
+        for _ in range(args.reps + 1):     # the first repetition warms
+            for q in arms:
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                engines[q].generate([5 + i % 1000
+                                     for i in range(args.prefill_len)],
+                                    max_new_tokens=1)
+                torch.cuda.synchronize()
+                pre[q].append((time.perf_counter() - t0) * 1e3)
+        for q in arms:
+            t = pre[q][1:]
+            print(f"{q[0] or 'bf16'} kv={q[1]} prefill {args.prefill_len} + 1 "
+                  f"token: {statistics.median(t):.1f} ms (min {min(t):.1f}, "
+                  f"max {max(t):.1f})", flush=True)
+    if args.perplexity:
+        # the arms share one random init (seed 0): the gap is the format's
+        root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+        with open(os.path.join(root, "README.md")) as f:
+            texts = [p for p in f.read().split("\n\n") if len(p) > 200][:32]
+        for q in arms:
+            print(f"{q[0] or 'bf16'} kv={q[1]} perplexity over {len(texts)} "
+                  f"README paragraphs: {engines[q].perplexity(texts):.2f}",
+                  flush=True)
     for q in arms:
         tps = statistics.median(r for r, _ in rates[q])
         n = rates[q][0][1]

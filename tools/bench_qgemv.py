@@ -41,9 +41,11 @@ def make_weights(N, K, copies, dev):
                        dtype=torch.uint8)
     s4 = torch.rand(N, K // GROUP, device=dev, generator=g) * 0.1 + 1e-2
     rep = lambda t: [t.clone() for _ in range(copies)]   # noqa: E731
+    w8, sw = ops.quant_fp8_rows(w)           # fp8 arm: int8's bytes
     # nf4 arm: the same random bytes read as level indices, s4 as absmax
     return {"bf16": rep(w), "q8": rep(q8), "s8": rep(s8), "q4": rep(q4),
-            "s4": rep(s4), "qn": rep(q4), "sn": rep(s4)}
+            "s4": rep(s4), "qn": rep(q4), "sn": rep(s4), "f8": rep(w8),
+            "sf": rep(sw)}
 
 
 def arms_for(M, W):
@@ -66,6 +68,13 @@ def arms_for(M, W):
                                                      GROUP)), b4)
     a["qgemv int8"] = (lambda x, i: ops.qlinear(x, W["q8"][i], W["s8"][i],
                                                 8), b8)
+    # fp8: activation quantized inside the kernel; skinny bf16 (twice the
+    # bytes) is what the same layer runs without --base-gemm fp8
+    a["qgemv fp8"] = (lambda x, i: ops.qlinear(x, W["f8"][i], W["sf"][i], 8,
+                                               codebook="e4m3"), b8)
+    if ops.skinny_supported(M, N, K):
+        a["skinny bf16"] = (lambda x, i: ops.skinny_linear(x, W["bf16"][i]),
+                            b16)
     a["qgemv int4"] = (lambda x, i: ops.qlinear(x, W["q4"][i], W["s4"][i],
                                                 4, GROUP), b4)
     a["qgemv nf4"] = (lambda x, i: ops.qlinear(x, W["qn"][i], W["sn"][i],
